@@ -8,14 +8,21 @@ RCCL all-reduce(MIN).  Inputs are resident in HBM before the timed region.  Two 
 (core.PoseLanes: consecutive steps alternate over two contexts on two HIP streams, so one step's drain overlaps
 the next step's fill; every step is still one full 10k-pose batch and completes inside the timed region).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--poses P] [--cpu-seconds S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--poses P] [--dump-outputs DIR] [--full [--cpu-seconds S]]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N
 
-Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields;
-cpu_reference_path times the reference's own CPU/OMP path, SURVEY.md row a14, on config C1).  The same line
-carries "c3": BASELINE.json configs[2] measured in the same run -- 5 objects x 10k candidate poses per GPU,
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set-up, warm-up, the K timed
+steps, and the line with metric / value / unit / ms_per_step and the workload's config and argmin.  --dump-outputs DIR
+writes what the last timed step computed (DUMP_NAMES) as DIR/<name>.npy; the inputs are seeded, so two builds of the
+project can be compared output for output.
+
+--full adds everything else to the same line (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields;
+cpu_reference_path times the reference's own CPU/OMP path, SURVEY.md row a14, on config C1): the rendered points per
+pose and the HIP-event and host timestamps of every timed step behind "roofline" and "host_timing", the CPU baselines,
+and "c3": BASELINE.json configs[2] measured in the same run -- 5 objects x 10k candidate poses per GPU,
 render + stride cloud + covariances + GICP + re-render + re-score + select per step (the north star's
-"rendered + GICP-refined + scored" figure), with its own roofline for the GICP kernel.
+"rendered + GICP-refined + scored" figure), with its own roofline for the GICP kernel.  --no-cpu, --cpu-seconds,
+--ref-cpu-seconds, --c3-steps and --c3-warmup shape those legs and mean nothing without --full.
 """
 from __future__ import annotations
 
@@ -262,6 +269,31 @@ def c3_leg(steps: int, warmup: int, local: int, rank: int, world: int, poses_per
     }
 
 
+DUMP_NAMES = ("rendered_cost", "observed_cost", "points_diff", "best_cost", "best_index")
+DUMP_MAX_POSES = 2_000_000  # 3 float32 costs + 1 float64 index per sampled pose: 40 MB
+
+
+def dump_outputs(path: str, costs, keys) -> None:
+    """--dump-outputs: what a caller of the timed step receives, from the last timed step -- the three per-pose
+    costs of core.evaluate (float32, one value per candidate pose of this rank's shard) and the per-model argmin
+    keys, decoded into cost and pose index (float64; both are integers far below 2^53, and the keys are the
+    all-reduced ones when several ranks run).  Beyond DUMP_MAX_POSES poses per step the costs are those of a fixed,
+    seeded sample of the poses, whose indices go beside them as sample_index (float64): under 64 MB in all."""
+    from perception_amd.core import decode_keys
+
+    os.makedirs(path, exist_ok=True)
+    cost, idx = decode_keys(keys)
+    arrays = [c.cpu().numpy().astype(np.float32) for c in costs]
+    n = len(arrays[0])
+    if n > DUMP_MAX_POSES:
+        pick = np.sort(np.random.default_rng(0).choice(n, size=DUMP_MAX_POSES, replace=False))
+        arrays = [a[pick] for a in arrays]
+        np.save(os.path.join(path, "sample_index.npy"), pick.astype(np.float64))
+    arrays += [np.asarray(cost, np.float64), np.asarray(idx, np.float64)]
+    for name, a in zip(DUMP_NAMES, arrays):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
 
@@ -301,6 +333,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--poses", type=int, default=10000, help="candidate poses per GPU per step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0's shard)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline and host-timing fields, the C3 (GICP) leg and the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--ref-cpu-seconds", type=float, default=6.0)
     ap.add_argument("--no-cpu", action="store_true")
@@ -311,6 +347,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # this process only waits for its N rank children
@@ -355,16 +393,17 @@ def main():
     keys_ring = [torch.full((w.num_models,), PCORE_KEY_NONE, dtype=torch.int64, device=dev) for _ in range(L)]
     works = [None] * L
 
-    # rendered points per pose (for the algorithmic byte count), measured once outside the timed region
-    # with one launch over the whole batch, so every fused-kernel launch of this process (and of its
-    # rocprofv3 --stats summary) covers the same n poses
     s = w.stride
-    hs, ws = (w.scene.height + s - 1) // s, w.scene.width // s
-    dbg = torch.empty((n, hs, ws), dtype=torch.int32, device=dev)
-    w.core.evaluate(w.poses, w.pose_model, w.pose_label, w.pose_obs_total, stride=s, dbg_zs=dbg)
-    p_r_mean = int((dbg > 0).sum().item()) / max(n, 1)
-    del dbg
-    torch.cuda.synchronize()
+    if args.full:
+        # rendered points per pose (for the algorithmic byte count), measured once outside the timed region
+        # with one launch over the whole batch, so every fused-kernel launch of this process (and of its
+        # rocprofv3 --stats summary) covers the same n poses
+        hs, ws = (w.scene.height + s - 1) // s, w.scene.width // s
+        dbg = torch.empty((n, hs, ws), dtype=torch.int32, device=dev)
+        w.core.evaluate(w.poses, w.pose_model, w.pose_label, w.pose_obs_total, stride=s, dbg_zs=dbg)
+        p_r_mean = int((dbg > 0).sum().item()) / max(n, 1)
+        del dbg
+        torch.cuda.synchronize()
 
     # host timestamps of every timed step (perf_counter, s): step start, around the wait for the lane's previous
     # exchange, around the launch call, after the exchange is issued -- they attribute a slow step to the host wait
@@ -403,8 +442,9 @@ def main():
             works[b] = None
     torch.cuda.synchronize()
 
-    # per-launch duration of the dominant (fused) kernel, by HIP events on the stream it runs on (its lane's)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
+    # (--full) per-launch duration of the dominant (fused) kernel, by HIP events on the stream it runs on (its lane's)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if args.full else None
+          for _ in range(args.steps)]
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -423,6 +463,35 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(args.steps - 1) % L], keys)
+    best_cost, best_idx = decode_keys(keys)
+    line = {
+        "metric": "candidate poses rendered+scored/sec @640x480",
+        "value": n * world * args.steps / elapsed,
+        "unit": "poses/s",
+        "n_gpus": joined,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (003_cracker_box proxy mesh, GT-rendered 16-bit depth + 2 mm noise, label mask)",
+        "config": {"workload": "C2: 1 YCB mesh (12,288 tris), 10k 6-DoF poses/GPU render+score, 640x480, "
+                               "stride 8, no ICP", "poses_per_gpu": n, "width": w.scene.width,
+                   "height": w.scene.height, "stride": s, "parallelism": f"pose-shard x{world}",
+                   "batches_in_flight": L, "ranks": joined, "devices": devices,
+                   "dist_backend": torch.distributed.get_backend() if pdist.exchange_active() else None,
+                   "exchange": ("all_reduce(MIN) of the int64 argmin keys per step" if pdist.exchange_active()
+                                else "none (one process)")},
+        "argmin": {"best_cost": int(best_cost[0]), "best_index": int(best_idx[0]), "gt_index": int(w.gt_index[0])},
+    }
+    if not args.full:
+        if rank == 0:
+            os.write(_JSON_FD, (json.dumps(line) + "\n").encode())
+        return
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
     # with L > 1 consecutive launches overlap (one's drain with the next one's fill), so a launch's own span
     # counts time it shares with its neighbours; the GPU time per launch is the union of the launch intervals
@@ -455,7 +524,6 @@ def main():
                       "the stage-COST launch on the lane's stream",
     }
 
-    best_cost, best_idx = decode_keys(keys)
     c3 = None
     if args.c3_steps > 0:
         del lanes, outs, keys_ring, works
@@ -463,8 +531,6 @@ def main():
         c3 = c3_leg(args.c3_steps, args.c3_warmup, local, rank, world)
     if rank != 0:
         return
-    total_poses = n * world * args.steps
-    value = total_poses / elapsed
     bpp = algorithmic_bytes_per_pose(w.scene.width, w.scene.height, s, p_r_mean)
     achieved = bpp * n / (busy_ms * 1e-3)
     traffic = None
@@ -532,30 +598,8 @@ def main():
                                              "the reference does) / kernel time; > 1 means faster than an "
                                              "HBM-bound materialising design could be"},
     }
-    line = {
-        "metric": "candidate poses rendered+scored/sec @640x480",
-        "value": value,
-        "unit": "poses/s",
-        "n_gpus": joined,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (003_cracker_box proxy mesh, GT-rendered 16-bit depth + 2 mm noise, label mask)",
-        "config": {"workload": "C2: 1 YCB mesh (12,288 tris), 10k 6-DoF poses/GPU render+score, 640x480, "
-                               "stride 8, no ICP", "poses_per_gpu": n, "width": w.scene.width,
-                   "height": w.scene.height, "stride": s, "parallelism": f"pose-shard x{world}",
-                   "batches_in_flight": L, "ranks": joined, "devices": devices,
-                   "dist_backend": torch.distributed.get_backend() if pdist.exchange_active() else None,
-                   "exchange": ("all_reduce(MIN) of the int64 argmin keys per step" if pdist.exchange_active()
-                                else "none (one process)")},
-        "roofline": roofline,
-        "host_timing": host_timing,
-        "argmin": {"best_cost": int(best_cost[0]), "best_index": int(best_idx[0]), "gt_index": int(w.gt_index[0])},
-    }
+    line["roofline"] = roofline
+    line["host_timing"] = host_timing
     if c3 is not None:
         line["c3"] = c3
     if world == 1 and not args.no_cpu:

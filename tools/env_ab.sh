@@ -13,7 +13,7 @@ fi
 for rep in $(seq 1 ${REPS:-2}); do
   for r in $RUNS; do
     L=${r%%:*}; E=${r#*:}
-    env PCORE_LIB=$PWD/build_ab/$L $E timeout -k 10 300 python bench.py --no-cpu ${BENCH_ARGS} > $OUT/envab.json 2> $OUT/envab.err || { tail -20 $OUT/envab.err; exit 1; }
+    env PCORE_LIB=$PWD/build_ab/$L $E timeout -k 10 300 python bench.py --full --no-cpu ${BENCH_ARGS} > $OUT/envab.json 2> $OUT/envab.err || { tail -20 $OUT/envab.err; exit 1; }
     python -c "import json; d=json.load(open('$OUT/envab.json')); print('$r: %.4gM poses/s  kernel %.4f ms' % (d['value']/1e6, d['roofline']['kernel_ms']))"
     if [ -n "$C5" ]; then
       env PCORE_LIB=$PWD/build_ab/$L $E timeout -k 10 300 python tools/bench_configs.py --configs C5 --steps 5 | cut -c1-150 || exit 1

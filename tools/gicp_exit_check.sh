@@ -8,7 +8,7 @@ mkdir -p $OUT; export TMPDIR=/tmp
 timeout -k 10 700 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -k "${TESTS:-gicp or icp or covariance}" \
   > $OUT/pytest_gicp.log 2>&1 || { tail -40 $OUT/pytest_gicp.log; exit 1; }
 tail -2 $OUT/pytest_gicp.log
-timeout -k 10 400 python -u bench.py --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python - "$OUT/bench.json" <<'EOF'
 import json, sys
 d = json.load(open(sys.argv[1]))

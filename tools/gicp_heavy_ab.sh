@@ -10,7 +10,7 @@ tail -1 $OUT/pytest.log
 for rep in 1 2; do
   for hm in default 0; do
     if [ $hm = default ]; then unset PCORE_GICP_HEAVY_MAX; else export PCORE_GICP_HEAVY_MAX=$hm; fi
-    timeout -k 10 300 python -u bench.py --no-cpu --steps 5 --c3-steps 5 > $OUT/bench_h${hm}_$rep.json 2> $OUT/bench_h${hm}_$rep.err \
+    timeout -k 10 300 python -u bench.py --full --no-cpu --steps 5 --c3-steps 5 > $OUT/bench_h${hm}_$rep.json 2> $OUT/bench_h${hm}_$rep.err \
       || { tail -20 $OUT/bench_h${hm}_$rep.err; exit 1; }
     python -c "import json; c=json.load(open('$OUT/bench_h${hm}_$rep.json'))['c3']; print('heavy_max=$hm C3 %.4g M  %.2f ms/step  gicp %.2f ms' % (c['value']/1e6, c['ms_per_step'], c['gicp']['gicp_ms_per_step']))"
   done

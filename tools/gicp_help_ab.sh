@@ -19,7 +19,7 @@ for k in 1 2; do
   run off perception_amd/libpcore.so 0 || exit 1
   run base ${BASE:-build_ab/base.so} 1 || exit 1
 done
-timeout -k 10 400 python -u bench.py --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --no-cpu > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python - "$OUT/bench.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

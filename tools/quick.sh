@@ -10,6 +10,6 @@ if [ -n "$TESTS" ]; then
   tail -2 $OUT/pytest_$TAG.log
 fi
 for i in $(seq 1 ${BENCH_REPS:-1}); do
-  timeout -k 10 300 python bench.py --no-cpu ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/bench_$TAG.json')); print('value %.4gM poses/s  kernel %.4f ms' % (d['value']/1e6, d['roofline']['kernel_ms']))"
 done

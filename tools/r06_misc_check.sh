@@ -10,9 +10,9 @@ cat $OUT/rccl_lane_check.json
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -k "${TESTS:-scan or rccl or distributed}" \
   > $OUT/pytest.log 2>&1 || { tail -40 $OUT/pytest.log; exit 1; }
 tail -2 $OUT/pytest.log
-timeout -k 10 400 python -u bench.py --no-cpu --force-pg --c3-steps 0 > $OUT/bench_force_pg.json 2> $OUT/bench_force_pg.err || { tail -20 $OUT/bench_force_pg.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --no-cpu --force-pg --c3-steps 0 > $OUT/bench_force_pg.json 2> $OUT/bench_force_pg.err || { tail -20 $OUT/bench_force_pg.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench_force_pg.json')); print('force-pg C2 %.4g M poses/s' % (d['value']/1e6), d['config']['dist_backend'], d['config']['exchange'], d['host_timing']['exchange_issue_ms'])"
-timeout -k 10 400 python -u bench.py --no-cpu --c3-steps 0 > $OUT/bench_no_pg.json 2> $OUT/bench_no_pg.err || { tail -20 $OUT/bench_no_pg.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --no-cpu --c3-steps 0 > $OUT/bench_no_pg.json 2> $OUT/bench_no_pg.err || { tail -20 $OUT/bench_no_pg.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench_no_pg.json')); print('no-pg C2 %.4g M poses/s' % (d['value']/1e6), d['config']['dist_backend'])"
 timeout -k 10 600 python -u tools/bench_configs.py --configs C2,C2scan_blob,C2scan_shell,C3scan > $OUT/configs_scan.jsonl 2> $OUT/configs_scan.err || { tail -20 $OUT/configs_scan.err; exit 1; }
 python -c "

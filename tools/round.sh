@@ -19,7 +19,7 @@ fi
 if [ -z "$SKIP_PMC" ]; then
   for C in FETCH_SIZE WRITE_SIZE; do
     echo "== pmc $C"
-    timeout -s KILL 180 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_${TAG}_$C -o run -- python bench.py --steps 3 --warmup 1 --no-cpu > $OUT/pmc_${TAG}_$C.json 2> $OUT/pmc_${TAG}_$C.err || { tail -20 $OUT/pmc_${TAG}_$C.err; exit 1; }
+    timeout -s KILL 180 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_${TAG}_$C -o run -- python bench.py --full --steps 3 --warmup 1 --no-cpu > $OUT/pmc_${TAG}_$C.json 2> $OUT/pmc_${TAG}_$C.err || { tail -20 $OUT/pmc_${TAG}_$C.err; exit 1; }
   done
   python tools/pmc_traffic.py $OUT/pmc_${TAG}_FETCH_SIZE/run_counter_collection.csv $OUT/pmc_${TAG}_WRITE_SIZE/run_counter_collection.csv profiles/pmc_traffic.json || exit 1
   cp profiles/pmc_traffic.json $OUT/pmc_traffic.json
@@ -33,10 +33,10 @@ if [ -z "$SKIP_PMC" ]; then
   cp profiles/sq_counters_gicp.json $OUT/sq_counters_gicp.json
 fi
 echo "== bench"
-timeout -k 10 600 python bench.py ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || { tail -20 $OUT/bench_$TAG.err; exit 1; }
 cat $OUT/bench_$TAG.json
 echo "== rocprof stats"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- python bench.py --no-cpu ${BENCH_ARGS} > $OUT/prof_bench_$TAG.json 2> $OUT/prof_$TAG.err || { tail -20 $OUT/prof_$TAG.err; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- python bench.py --full --no-cpu ${BENCH_ARGS} > $OUT/prof_bench_$TAG.json 2> $OUT/prof_$TAG.err || { tail -20 $OUT/prof_$TAG.err; exit 1; }
 cat $OUT/prof_bench_$TAG.json
 python tools/trace_busy.py $OUT/prof_$TAG/run_kernel_trace.csv --last ${STEPS:-20} --sq profiles/sq_counters.json --out $OUT/trace_busy_$TAG.json --stats-out $OUT/c2_kernel_stats_$TAG.csv || exit 1
 find $OUT -path "*_$TAG*" -name "*.csv" | head -20
