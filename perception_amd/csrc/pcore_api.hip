@@ -755,7 +755,8 @@ static hipError_t set_fused_tiles(pcore_ctx* c, int num_poses, FusedArgs& a, hip
 static int ensure_sampled(pcore_ctx* c, int stride, hipStream_t s) {
     if (c->sampled_stride == stride) return PCORE_OK;
     c->generation++;  // a captured graph would read a source sampled at another stride
-    const int ws = (c->cam.width + stride - 1) / stride, hs = (c->cam.height + stride - 1) / stride;
+    // the callers' sampled image (validate_eval guarantees width % stride == 0)
+    const int ws = c->cam.width / stride, hs = (c->cam.height + stride - 1) / stride;
     HIPC(c, dev_reserve(c->src_s, (size_t)ws * hs));
     HIPC(c, dev_reserve(c->lab_s, (size_t)ws * hs));
     HIPC(c, launch_sample_source(c->src_depth.p, c->src_mask.p, c->cam.width, c->cam.height, stride, c->src_s.p,

@@ -65,24 +65,12 @@ def test_gpu_covariances_equal_oracle_bitwise(k):
 
 
 def _grid_clouds(cam_name="640"):
-    """Clouds unprojected from a stride-8 sample grid of the camera (what render_cloud writes): tilted planes, a step
-    (a depth discontinuity inside the neighbourhoods), 24 to 1,000 points -- the last one's window (40 x 25 cells) is
-    larger than the kernel's LDS map, which sends it to the brute force."""
+    """tests.helpers.grid_clouds on the stride-8 sample grid of the camera (other strides and an fx != fy camera:
+    tests/test_gpu_geometry.py)."""
     from perception_amd import synthetic as syn
+    from tests.helpers import grid_clouds
     cam, s = (syn.CAM_640 if cam_name == "640" else syn.CAM_1280), 8
-    rng = np.random.default_rng(9)
-    clouds = []
-    for (w, h, x0, y0) in ((12, 10, 30, 20), (23, 20, 10, 5), (8, 3, 50, 40), (27, 17, 3, 30), (40, 25, 20, 10)):
-        kx, ky = np.meshgrid(np.arange(x0, x0 + w), np.arange(y0, y0 + h))
-        u, v = kx * s, ky * s
-        z = 0.8 + 0.0004 * (u - cam["cx"]) + 0.0003 * (v - cam["cy"]) + rng.normal(size=u.shape) * 1e-3
-        if w == 27:
-            z = np.where(kx > x0 + 13, z + 0.05, z)  # a step: the far side's neighbourhoods reach across it
-        z = np.round(z * 100) / 100  # the int-centimetre z-buffer's depths
-        x = ((u.astype(np.float32) - np.float32(cam["cx"])) / np.float32(cam["fx"]) * z.astype(np.float32))
-        y = ((v.astype(np.float32) - np.float32(cam["cy"])) / np.float32(cam["fy"]) * z.astype(np.float32))
-        clouds.append(np.stack([x, y, z.astype(np.float32)], -1).reshape(-1, 3).astype(np.float32))
-    return clouds, cam, s
+    return grid_clouds(cam, s), cam, s
 
 
 @pytest.mark.parametrize("cam_name", ["640", "1280"])

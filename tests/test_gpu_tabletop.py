@@ -10,17 +10,17 @@ import oracle
 from perception_amd import synthetic as syn
 from perception_amd.recognizer import CameraIntrinsics, ModelMetaData, preprocessing_transform
 from perception_amd.tabletop import TableParams, TabletopRecognizer, pr2_gpu_params
-from tests.helpers import oracle_render_fn
+from tests.helpers import ROMAN_640, oracle_render_fn
 
 pytestmark = pytest.mark.gpu
 
 
-def _scene(colors=None):
+def _scene(colors=None, cam=syn.CAM_640):
     names = ["003_cracker_box", "005_tomato_soup_can"]
     placements = [(0.60, -0.08, 0.4), (0.64, 0.10, 0.0)]
     bank = syn.model_bank(names)
     pre = [preprocessing_transform(m, six_dof=False) for m in bank.models]
-    sc = syn.make_tabletop_scene(names, placements, pre, oracle_render_fn, table_height=0.7,
+    sc = syn.make_tabletop_scene(names, placements, pre, oracle_render_fn, table_height=0.7, cam=cam,
                                  rng=np.random.default_rng(4), colors=colors)
     return names, placements, sc
 
@@ -63,22 +63,34 @@ def test_tabletop_localization_matches_oracle(cylinder):
     assert len(res) >= 1
 
 
-@pytest.mark.parametrize("tile", ["auto", "tcap64"])
-def test_tabletop_colour_cost_matches_oracle(tile, monkeypatch):
+@pytest.mark.parametrize("tile,gpu_stride,cam_name", [
+    pytest.param("auto", 4, "640", id="auto"), pytest.param("tcap64", 4, "640", id="tcap64"),
+    pytest.param("auto", 8, "640", id="auto-s8"), pytest.param("tcap64", 8, "640", id="tcap64-s8"),
+    pytest.param("auto", 5, "640", id="auto-s5"), pytest.param("tcap64", 5, "640", id="tcap64-s5"),
+    pytest.param("auto", 5, "roman", id="auto-s5-roman")])
+def test_tabletop_colour_cost_matches_oracle(tile, gpu_stride, cam_name, monkeypatch):
     """cost_type 1: the colour id pass (nearest fragment's triangle) and the CIEDE2000 gate, bit-exact -- with
     the chosen LDS tile and with a 64-sample tile that scores nearly every pose in chunks of the tile (the colour
-    ids are indexed within the chunk)."""
+    ids are indexed within the chunk).  The colour kernel is the generic-stride instantiation at every stride: the
+    reference's stride 4, stride 8 (which the depth costs serve with the constant-stride kernel), stride 5, and
+    stride 5 on the reference's 640 x 480 camera with fx != fy."""
     if tile == "tcap64":
         monkeypatch.setenv("PCORE_FUSED_TCAP", "64")
-    names, placements, sc = _scene(colors=[(200, 40, 30), (30, 60, 190)])
+    names, placements, sc = _scene(colors=[(200, 40, 30), (30, 60, 190)],
+                                   cam=syn.CAM_640 if cam_name == "640" else ROMAN_640)
     table = TableParams(x_min=0.52, x_max=0.68, y_min=-0.16, y_max=0.16, table_height=0.7, res=0.04)
     bank = {n: ModelMetaData(n, model=sc.bank.models[i]) for i, n in enumerate(names)}
     cam = CameraIntrinsics(sc.width, sc.height, sc.fx, sc.fy, sc.cx, sc.cy)
-    rec = TabletopRecognizer(bank, cam, table, pr2_gpu_params())
-    assert rec.params.use_color_cost
+    # IsValidPose's neighbour count scales with the cloud's density, 1 / stride^2 (30 at the reference's stride 4)
+    rec = TabletopRecognizer(bank, cam, table, pr2_gpu_params(
+        gpu_stride=gpu_stride, min_neighbor_points_for_valid_pose=round(30 * 16 / gpu_stride ** 2)))
+    assert rec.params.use_color_cost and rec.params.gpu_stride == gpu_stride
+    assert gpu_stride != 4 or rec.params.min_neighbor_points_for_valid_pose == 30
+    assert sc.fx == sc.fy if cam_name == "640" else sc.fx != sc.fy
     res = rec.localize(names, sc.depth_raw, sc.camera_pose, sc.depth_factor, rgb=sc.rgb)
     assert rec.use_colour and rec._cost_type() == 1
     states = rec.generate_successor_states()
+    assert len(states) >= 16
     mats = rec._pose_in_cam(states)
     pm = np.array([s[0] for s in states], np.int32)
     tot = rec._obs_totals(states)
