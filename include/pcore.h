@@ -185,6 +185,40 @@ int pcore_evaluate_icp(pcore_ctx* ctx, const float* d_poses, const int32_t* d_po
                        int32_t* d_out_iters, float* d_out_rc, float* d_out_oc, float* d_out_diff,
                        pcore_stream stream);
 
+/* Planar (x, y, yaw) ICP of the 3-DoF search (ComputeGreedyCostsInParallelGPU with icp_type 0 and use_icp 1,
+ * search_env.cpp:1843-1973: GetICPAdjustedPosesCPU -> GetICPAdjustedPose, 1198-1299, 6235-6396, a PCL ICP with
+ * TransformationEstimation2D on the host between the two GPU passes).  The loop is the build's own spec modelled on
+ * PCL's ("Planar ICP spec"); the defaults are the reference's settings. */
+typedef struct pcore_planar_icp_params {
+    int32_t max_iterations;         /* 20  (max_icp_iterations) */
+    float   max_correspondence;     /* 0.05 m (icp_max_correspondence) */
+    double  transformation_epsilon; /* 1e-8 */
+    double  fitness_epsilon;        /* 1e-5 */
+} pcore_planar_icp_params;
+
+/* Render every pose at stage CLOUD (stride samples, 3-DoF source occlusion: the slots pcore_evaluate_icp feeds GICP)
+ * and align each cloud to the observation -- its points in the order given to pcore_set_observation -- in the plane:
+ * both are moved to the world frame by world_from_cam (HOST, 4 x 4 row-major float, each row left to right in float)
+ * and only x, y and yaw move.  d_out_xform: N x 4 doubles (c, s, tx, ty), the cumulative world-frame transform
+ * x' = c x - s y + tx, y' = s x + c y + ty; d_out_iters: estimation steps done; d_out_status: 0 = iteration cap,
+ * 1 = transform threshold, 2 = absolute mse, 3 = relative mse, 4 = fewer than 3 correspondences (identity), 5 = empty
+ * render (identity, 0 iterations); d_out_mse (nullable): the last iteration's mean squared correspondence distance (0
+ * for status 4 and 5).  Only the 3-DoF cost types (0, 1) are accepted; there are no pose labels.  Every argument is
+ * checked before the first launch.  The batch is split into equal chunks that fit a scratch budget of min(32 GiB, 40 %
+ * of the free device memory) at 16 B per pose and stride sample.  The observation's world-frame copy and its
+ * neighbour grid (cells >= 2 max_correspondence) are built on first use and kept while the observation, the matrix
+ * bytes and the radius stay the same; a capturing stream that would need that build, or new scratch, gets
+ * PCORE_E_STATE (run the call once before the capture). */
+int pcore_icp_planar(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_model, int32_t num_poses,
+                     const pcore_eval_params* params, const float* world_from_cam,
+                     const pcore_planar_icp_params* icp, double* d_out_xform, int32_t* d_out_iters,
+                     int32_t* d_out_status, double* d_out_mse, pcore_stream stream);
+
+/* Test hook (no reference counterpart): the planar ICP's estimation step (TransformationEstimation2D on raw sums,
+ * DESIGN.md section 5) of n records of 10 doubles -- n, sum qx, sum qy, sum tx, sum ty, sum qx tx, sum qx ty,
+ * sum qy tx, sum qy ty, sum d^2 -- into d_out (n x 4: c', s', tx', ty'), one thread each. */
+int pcore_debug_planar_step(const double* d_sums, double* d_out, int32_t n, pcore_stream stream);
+
 /* Stage "RENDER" / "DEBUG" images (renderer.cu:1594-1615): full-resolution int32 z-buffers (cm) with source
  * occlusion and INT_MAX -> 0 (image_render, image_renderer.cuh:336-496).  d_out_depth: N x H x W.
  * d_out_color (nullable): the reference's result_color -- three planes red, green, blue of N x H x W uint8 each,

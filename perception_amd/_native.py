@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "pcore_observed_cloud_bounded", "pcore_set_observation_colors", "pcore_generation", "pcore_get_stats",
     "pcore_count_within", "pcore_state_poses", "pcore_evaluate_select", "pcore_get_tile_info", "pcore_debug_lm_solve",
     "pcore_debug_covariances", "pcore_debug_covariances_cloud", "pcore_debug_gicp_help_stats", "pcore_depth_to_cloud_ex",
+    "pcore_icp_planar", "pcore_debug_planar_step",
 )
 
 
@@ -76,6 +77,21 @@ class IcpParams(ctypes.Structure):
                 ("rotation_epsilon", ctypes.c_double), ("transformation_epsilon", ctypes.c_double),
                 ("cycle_exit_window", ctypes.c_int32)]
 
+
+class PlanarIcpParams(ctypes.Structure):
+    """pcore_planar_icp_params (include/pcore.h)."""
+    _fields_ = [("max_iterations", ctypes.c_int32), ("max_correspondence", ctypes.c_float),
+                ("transformation_epsilon", ctypes.c_double), ("fitness_epsilon", ctypes.c_double)]
+
+
+# GetICPAdjustedPose's settings (search_env.cpp:6235-6396; env_config.yaml max_icp_iterations, icp_max_correspondence)
+PLANAR_MAX_ITER = 20
+PLANAR_MAX_CORRESPONDENCE = 0.05
+PLANAR_TRANS_EPS = 1e-8
+PLANAR_FIT_EPS = 1e-5
+# pcore_icp_planar's status values
+PLANAR_ITERATION_CAP, PLANAR_TRANSFORM, PLANAR_ABS_MSE, PLANAR_REL_MSE, PLANAR_NO_CORRESPONDENCES, PLANAR_EMPTY_RENDER = \
+    range(6)
 
 # renderer.cu:1696-1699
 ICP_K = 10
@@ -144,6 +160,11 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                               ctypes.POINTER(i32), vp]
     L.pcore_depth_to_cloud.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32,
                                        ctypes.POINTER(i32), vp]
+    if hasattr(L, "pcore_icp_planar"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_icp_planar.argtypes = [vp, vp, vp, i32, ctypes.POINTER(EvalParams), ctypes.POINTER(ctypes.c_float),
+                                       ctypes.POINTER(PlanarIcpParams), vp, vp, vp, vp, vp]
+    if hasattr(L, "pcore_debug_planar_step"):
+        L.pcore_debug_planar_step.argtypes = [vp, vp, i32, vp]
     L.pcore_select.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp]
     L.pcore_pose_distances.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.pcore_set_observation_colors.argtypes = [vp, vp, i32, vp]

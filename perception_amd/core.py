@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import Camera, EvalParams, IcpParams, PcoreError
+from ._native import Camera, EvalParams, IcpParams, PcoreError, PlanarIcpParams
 
 
 def _ptr(t: Optional[torch.Tensor], dtype: torch.dtype, name: str):
@@ -241,6 +241,44 @@ class PoseCore:
             _ptr(iters, torch.int32, "iterations"), _ptr(rc, torch.float32, "rc"), _ptr(oc, torch.float32, "oc"),
             _ptr(df, torch.float32, "diff"), _stream(stream)))
         return adj, iters, rc, oc, df
+
+    def icp_planar(self, poses: torch.Tensor, pose_model: torch.Tensor, world_from_cam: np.ndarray,
+                   cost_type: int = _native.COST_DEPTH_3DOF, stride: int = 4, depth_factor: float = 100.0,
+                   occlusion_threshold: float = 1.0, max_iterations: int = _native.PLANAR_MAX_ITER,
+                   max_correspondence: float = _native.PLANAR_MAX_CORRESPONDENCE,
+                   transformation_epsilon: float = _native.PLANAR_TRANS_EPS,
+                   fitness_epsilon: float = _native.PLANAR_FIT_EPS, out=None, stream=None):
+        """Planar (x, y, yaw) ICP of every pose's rendered stride-sample cloud onto the observation, both moved to the
+        world frame by world_from_cam (4 x 4; pcore_icp_planar).  Returns (xform (N, 4) float64: c s tx ty, iterations
+        (N,) int32, status (N,) int32, mse (N,) float64) on the GPU."""
+        n = int(poses.shape[0])
+        dev = poses.device
+        if out is None:
+            out = (torch.empty((n, 4), dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
+        xform, iters, status, mse = out
+        p = EvalParams(int(cost_type), 0, int(stride), float(depth_factor), 0.0, float(occlusion_threshold), 0.0)
+        pp = PlanarIcpParams(int(max_iterations), float(max_correspondence), float(transformation_epsilon),
+                             float(fitness_epsilon))
+        M = (ctypes.c_float * 16)(*np.asarray(world_from_cam, np.float32).reshape(16))
+        self._check(self.lib.pcore_icp_planar(
+            self._h, _ptr(poses, torch.float32, "poses"), _ptr(pose_model, torch.int32, "pose_model"), n,
+            ctypes.byref(p), M, ctypes.byref(pp), _ptr(xform, torch.float64, "xform"),
+            _ptr(iters, torch.int32, "iterations"), _ptr(status, torch.int32, "status"),
+            _ptr(mse, torch.float64, "mse"), _stream(stream)))
+        return xform, iters, status, mse
+
+    def planar_step(self, sums: torch.Tensor, stream=None) -> torch.Tensor:
+        """pcore_debug_planar_step: the planar ICP's estimation step of (n, 10) float64 raw sum records -> (n, 4)
+        float64 (c', s', tx', ty')."""
+        sums = sums.contiguous()
+        n = int(sums.shape[0])
+        out = torch.empty((n, 4), dtype=torch.float64, device=sums.device)
+        rc = self.lib.pcore_debug_planar_step(_ptr(sums, torch.float64, "sums"), _ptr(out, torch.float64, "out"), n,
+                                              _stream(stream))
+        if rc != _native.PCORE_OK:
+            raise PcoreError(rc, "pcore_debug_planar_step failed")
+        return out
 
     def render(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
                occlusion_threshold: float = 1.0, out: Optional[torch.Tensor] = None, color: bool = False,

@@ -6,6 +6,7 @@
 #include "pcore_internal.h"
 #include "pcore_streams.h"
 #include "pcore_gicp_math.h"
+#include "pcore_icp2d_math.h"
 
 #include <algorithm>
 #include <climits>
@@ -123,6 +124,16 @@ struct pcore_ctx {
     std::vector<hipEvent_t> icp_ev;
     int icp_ev_used = 0;
     double peak_mem_mb = 0.0;
+    // planar ICP (pcore_icp_planar): the observation as set (host copy, caller's order), its world-frame copy and
+    // neighbour grid, built on first use and kept while (observation, matrix bytes, radius) stay the same
+    std::vector<float> obs_xyz_h;
+    uint64_t obs_serial = 0;          // counts pcore_set_observation calls
+    uint64_t planar_obs_serial = 0;   // the observation the grid below was built from (0: none)
+    float planar_m[16] = {};
+    float planar_radius = 0.0f;
+    LabelGrid planar_grid{};
+    DevBuf<int32_t> planar_cell_start;
+    DevBuf<float4> planar_pts;
 };
 
 namespace {
@@ -328,6 +339,7 @@ void pcore_destroy(pcore_ctx* c) {
     (void)dev_free(c->icp_cloud); (void)dev_free(c->icp_count); (void)dev_free(c->icp_cov); (void)dev_free(c->icp_corr); (void)dev_free(c->icp_corr_hist); (void)dev_free(c->scratch_dc_pre); (void)dev_free(c->icp_mahal); (void)dev_free(c->icp_counter); (void)dev_free(c->icp_iter_stats); (void)dev_free(c->icp_help_ctl); (void)dev_free(c->icp_help_gran); (void)dev_free(c->icp_order_keys); (void)dev_free(c->icp_order_idx); (void)dev_free(c->icp_order_temp);
     (void)dev_free(c->stri_orig); (void)dev_free(c->tri_lab); (void)dev_free(c->obs_lab); (void)dev_free(c->colour_id);
     (void)dev_free(c->metric_part); (void)dev_free(c->tri_rgb); (void)dev_free(c->render_tri);
+    (void)dev_free(c->planar_cell_start); (void)dev_free(c->planar_pts);
     for (hipEvent_t e : c->icp_ev) (void)hipEventDestroy(e);
     delete c;
 }
@@ -560,6 +572,8 @@ int pcore_set_observation(pcore_ctx* c, const int32_t* d_src_depth_cm, const uin
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return lab[a] < lab[b]; });
     c->obs_order = order;
     c->have_obs_colours = false;
+    c->obs_xyz_h = xyz;  // pcore_icp_planar's targets, in the caller's order
+    c->obs_serial++;
     std::vector<LabelGrid> grids(num_labels + 1);
     std::vector<int32_t> cell_start;
     std::vector<float4> gpts;
@@ -1143,6 +1157,138 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     // re-render and re-score the adjusted poses (renderer.cu:1757-1907)
     return pcore_evaluate(c, d_out_poses, d_pose_model, d_pose_label, d_pose_obs_total, num_poses, p, d_out_rc,
                           d_out_oc, d_out_diff, nullptr, stream);
+}
+
+// Planar ICP between the two passes of the 3-DoF search (GetICPAdjustedPosesCPU, search_env.cpp:1198-1299): stage
+// CLOUD into per-pose slots (launch_render_cloud, as pcore_evaluate_icp's first step), then planar_icp_kernel over
+// the slots.  Every check comes before the first launch, so an invalid call writes nothing.
+int pcore_icp_planar(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, int32_t num_poses,
+                     const pcore_eval_params* p, const float* world_from_cam, const pcore_planar_icp_params* pp,
+                     double* d_out_xform, int32_t* d_out_iters, int32_t* d_out_status, double* d_out_mse,
+                     pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (!p || !pp || !world_from_cam) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: null parameters");
+    if (!c->have_mesh || !c->have_cam || !c->have_obs)
+        return fail(c, PCORE_E_STATE, "icp_planar: meshes, camera and observation must be set first");
+    if (p->cost_type != PCORE_COST_DEPTH_3DOF && p->cost_type != PCORE_COST_RGBD_3DOF)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: cost_type must be a 3-DoF one (0 or 1)");
+    if (pp->max_iterations < 0) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: max_iterations must be >= 0");
+    if (!std::isfinite(pp->max_correspondence) || pp->max_correspondence < 0.0f)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: max_correspondence must be finite and >= 0");
+    if (std::isnan(pp->transformation_epsilon) || std::isnan(pp->fitness_epsilon))
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: NaN epsilon");
+    for (int i = 0; i < 16; i++)
+        if (!std::isfinite(world_from_cam[i])) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: non-finite world_from_cam");
+    if (num_poses < 0 || (num_poses > 0 && (!d_poses || !d_pose_model || !d_out_xform || !d_out_iters || !d_out_status)))
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: null pose / output pointer");
+    const int W = c->cam.width, H = c->cam.height;
+    if (p->stride <= 0 || W % p->stride != 0)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: width must be a multiple of stride");
+    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
+    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: sampled image too large");
+    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: sampled z-buffer does not fit in LDS (use a larger stride)");
+    if (num_poses == 0) return PCORE_OK;
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nsamp = ws * hs;
+    // chunks by the scratch budget, as pcore_evaluate_icp: a slot of nsamp points (16 B) and a count per pose, at most
+    // min(32 GiB, 40 % of the free device memory); PCORE_ICP2D_SCRATCH_BYTES sets the budget (test / A/B knob)
+    const size_t per_pose = (size_t)nsamp * sizeof(float4) + sizeof(int32_t);
+    size_t budget = (size_t)32 << 30;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+            budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
+    }
+    if (const char* e = getenv("PCORE_ICP2D_SCRATCH_BYTES")) budget = (size_t)std::max(1LL, atoll(e));
+    const int max_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_pose), 0x7fffffff);
+    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
+    const int chunk = (num_poses + nchunks - 1) / nchunks;
+    // what has to be built or allocated first; none of it may happen while the stream captures
+    const bool grid_stale = c->planar_obs_serial != c->obs_serial ||
+                            std::memcmp(c->planar_m, world_from_cam, sizeof(c->planar_m)) != 0 ||
+                            std::memcmp(&c->planar_radius, &pp->max_correspondence, sizeof(float)) != 0;
+    const bool setup = grid_stale || c->sampled_stride != p->stride || !c->icp_cloud.p || !c->icp_count.p ||
+                       c->icp_cloud.n < (size_t)chunk * nsamp || c->icp_count.n < (size_t)chunk;
+    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap_status) != hipSuccess) {
+        (void)hipGetLastError();
+        cap_status = hipStreamCaptureStatusActive;
+    }
+    if (setup && cap_status != hipStreamCaptureStatusNone)
+        return fail(c, PCORE_E_STATE, "icp_planar: the world-frame grid or the scratch would have to be built while the "
+                                      "stream captures; run the call once before the capture");
+    if (grid_stale) {
+        const int n = (int)(c->obs_xyz_h.size() / 3);
+        std::vector<float4> wp((size_t)n);
+        for (int i = 0; i < n; i++) {
+            float4 q;
+            icp2d::to_world(world_from_cam, c->obs_xyz_h[3 * (size_t)i], c->obs_xyz_h[3 * (size_t)i + 1],
+                            c->obs_xyz_h[3 * (size_t)i + 2], q.x, q.y, q.z);
+            std::memcpy(&q.w, &i, 4);
+            wp[i] = q;
+        }
+        std::vector<int32_t> cell_start;
+        std::vector<float4> gpts;
+        LabelGrid g;
+        build_grid(wp, pp->max_correspondence, g, cell_start, gpts);
+        if (gpts.empty()) gpts.push_back(make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        HIPC(c, hipStreamSynchronize(s));  // an earlier call on the stream may still read the old grid
+        c->planar_obs_serial = 0;
+        c->generation++;
+        HIPC(c, dev_upload(c->planar_cell_start, cell_start));
+        HIPC(c, dev_upload(c->planar_pts, gpts));
+        c->planar_grid = g;
+        std::memcpy(c->planar_m, world_from_cam, sizeof(c->planar_m));
+        c->planar_radius = pp->max_correspondence;
+        c->planar_obs_serial = c->obs_serial;
+    }
+    int rc = ensure_sampled(c, p->stride, s);
+    if (rc != PCORE_OK) return rc;
+    HIPC(c, reserve_gen(c, c->icp_cloud, (size_t)chunk * nsamp));
+    HIPC(c, reserve_gen(c, c->icp_count, (size_t)chunk));
+    FusedArgs a{};
+    fill_fused_args(c, p, a);
+    PlanarArgs g{};
+    g.src = c->icp_cloud.p;
+    g.src_count = c->icp_count.p;
+    g.src_cap = nsamp;
+    for (int i = 0; i < 12; i++) g.m[i] = world_from_cam[i];
+    g.grid = c->planar_grid;
+    g.cell_start = c->planar_cell_start.p;
+    g.grid_pts = c->planar_pts.p;
+    g.r = pp->max_correspondence;
+    g.r2 = pp->max_correspondence * pp->max_correspondence;
+    g.max_iter = pp->max_iterations;
+    g.eps_t = pp->transformation_epsilon;
+    g.eps_fit = pp->fitness_epsilon;
+    g.out_xform = d_out_xform;
+    g.out_iters = d_out_iters;
+    g.out_status = d_out_status;
+    g.out_mse = d_out_mse;
+    for (int base = 0; base < num_poses; base += chunk) {
+        const int n = std::min(chunk, num_poses - base);
+        a.poses = d_poses + (size_t)16 * base;
+        a.pose_model = d_pose_model + base;
+        a.pose_label = nullptr;
+        a.num_poses = n;
+        a.cloud_out = c->icp_cloud.p;
+        a.cloud_count = c->icp_count.p;
+        a.cloud_cap = nsamp;
+        a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
+        if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
+        if (a.tcap <= 0) a.tcap = a.ws * a.hs;
+        HIPC(c, launch_render_cloud(a, s));
+        g.pose_base = base;
+        HIPC(c, launch_planar_icp(g, n, s));
+    }
+    return PCORE_OK;
+}
+
+int pcore_debug_planar_step(const double* d_sums, double* d_out, int32_t n, pcore_stream stream) {
+    if (n < 0 || (n > 0 && (!d_sums || !d_out))) return PCORE_E_INVALID_ARG;
+    return launch_planar_step_test(d_sums, d_out, n, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
 }
 
 int pcore_render(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,

@@ -286,6 +286,29 @@ hipError_t launch_state_poses(const double* states, const int32_t* model, const 
 hipError_t launch_count_within(const float* q, const int32_t* labels, const float* r2, int n, const float4* pts,
                                const int32_t* seg_lo, const int32_t* seg_hi, int num_segs, int32_t* out,
                                hipStream_t s);
+// pcore_icp2d.hip: planar (x, y, yaw) ICP over a chunk of poses ("Planar ICP spec")
+struct PlanarArgs {
+    float4* src;               // chunk-local per-pose slots (src + pose * src_cap), camera frame in; the kernel
+                               // rewrites each slot in place with its world-frame points
+    const int32_t* src_count;
+    int32_t src_cap;
+    float m[12];               // rows 0..2 of world_from_cam
+    LabelGrid grid;            // the world-frame observation's grid (cells >= 2 * max_correspondence; cell_base 0)
+    const int32_t* cell_start;
+    const float4* grid_pts;    // cell-sorted world-frame targets (x, y, z, bitcast(index as set))
+    float r, r2;               // max_correspondence and float(r) * float(r)
+    int32_t max_iter;
+    double eps_t, eps_fit;
+    double* out_xform;         // batch-global: N x 4 (c, s, tx, ty)
+    int32_t* out_iters;
+    int32_t* out_status;
+    double* out_mse;           // nullable
+    int32_t pose_base;         // first batch index of this chunk
+};
+// one one-wave workgroup per pose of the chunk
+hipError_t launch_planar_icp(const PlanarArgs& a, int num_poses, hipStream_t s);
+// test hook: icp2d::step of n raw sum records (10 doubles each), one thread each (pcore_debug_planar_step)
+hipError_t launch_planar_step_test(const double* sums, double* out, int n, hipStream_t s);
 // pcore_metrics.hip
 int pose_dist_blocks(int n);
 hipError_t launch_pose_distances(const float* pts, int n, const double* T_gt, const double* T_est, int pairs,

@@ -48,6 +48,8 @@ PERCH_PARAM_DEFAULTS = {
     "gpu_occlusion_threshold": ("gpu_occlusion_threshold", 1.0),
     "depth_median_blur": ("depth_median_blur", 17.0),
     "icp_type": ("icp_type", 0),
+    "max_icp_iterations": ("max_icp_iterations", 10),
+    "icp_max_correspondence": ("icp_max_correspondence", 0.05),
     "use_model_specific_search_resolution": ("use_model_specific_search_resolution", False),
 }
 # object_recognizer.cpp:57-77
@@ -225,7 +227,9 @@ def run(output_dir_name: str, ps: ParamServer, device: Optional[int] = None) -> 
         if params.use_color_cost and colour:
             img = _read_image(str(colour))
             rgb = np.ascontiguousarray(img[..., :3][..., ::-1]) if img.ndim == 3 else None
-        res = rec.localize(names, depth, camera_pose, depth_factor, rgb)
+        # /use_icp with icp_type 0: the planar ICP between the two GPU passes.  perch_fat.cpp:143 reads the parameter
+        # without a default (the field stays uninitialised); absent means off here
+        res = rec.localize(names, depth, camera_pose, depth_factor, rgb, use_icp=int(ps.get("/use_icp", 0)))
         result = rec.localization_result(res)
     elapsed = time.perf_counter() - t0
     if world > 1:

@@ -60,6 +60,9 @@ class PerchParams:
     icp_max_iterations: int = ICP_MAX_ITER
     icp_rotation_epsilon: float = ICP_ROT_EPS
     icp_transformation_epsilon: float = ICP_TRANS_EPS
+    # the 3-DoF planar ICP (icp_type 0; env_config.yaml max_icp_iterations, icp_max_correspondence)
+    max_icp_iterations: int = 20
+    icp_max_correspondence: float = 0.05
 
 
 @dataclass
@@ -456,6 +459,11 @@ class ObjectRecognizer:
         mats = chain_matmul_batch(cam_matrix, pose_matrix_batch(P[:, :3], P[:, 3:7]), pre)
         return init_from_eigen_batch(mats, 100)
 
+    def _planar_refine(self, states: States, poses: torch.Tensor, pm: torch.Tensor):
+        """icp_type 0 with use_icp: the states refined before they are scored -> (states, poses, seconds).  Only the
+        3-DoF search has such a stage (TabletopRecognizer); here the states pass through."""
+        return states, poses, 0.0
+
     # -- ComputeGreedyRenderPoses (search_env.cpp:2462-2651) ----------------------------------------
     def compute_greedy_render_poses(self, inp: RecognitionInput):
         t0 = time.perf_counter()
@@ -491,6 +499,11 @@ class ObjectRecognizer:
                 mine = states[lo:hi]
                 poses = self._poses_device(mine)
                 pm = torch.from_numpy(mine.model.copy()).to(self.device)
+                if p.icp_type == 0 and inp.use_icp:
+                    # the 3-DoF flow of ComputeGreedyCostsInParallelGPU (search_env.cpp:1843-1973): stage CLOUD and the
+                    # planar ICP of every state, then everything below (labels, totals, stage COST, the selection,
+                    # the cost dump) runs on the adjusted states
+                    mine, poses, icp_time = self._planar_refine(mine, poses, pm)
                 pl = self._pose_labels(mine)
                 tot = torch.from_numpy(self._obs_totals(mine)).to(self.device)
             cost_type = self._cost_type()

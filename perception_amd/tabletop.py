@@ -19,8 +19,12 @@ region.  Mirrors, on top of PoseCore:
                                               yaw * pitch * roll quaternion)
 
 Scoring is the GPU hot path with cost_type 0 (depth) -- or 1 (colour gate) once the observation has
-colours -- and no pose labels.  Differences from the reference: the projected cloud is the stride-1
-bounded GPU cloud moved to the world frame (the reference builds it on the CPU with PCL from the same
+colours -- and no pose labels.  With use_icp the grid states are refined between two GPU passes as
+ComputeGreedyCostsInParallelGPU does with icp_type 0 (search_env.cpp:1843-1973): stage CLOUD and a planar (x, y, yaw)
+ICP per state on the device (PoseCore.icp_planar, the seam of GetICPAdjustedPosesCPU), GetICPAdjustedPose's pose
+update on the host (planar_adjusted_states), then stage COST on the adjusted states.
+
+Differences from the reference: the projected cloud is the stride-1 bounded GPU cloud moved to the world frame (the reference builds it on the CPU with PCL from the same
 depth image, GetGravityAlignedPointCloud, search_env.cpp:4475-4600, without downsampling by default); the
 8-bit depth images (the reference's non-16-bit branch, search_env.cpp:5916-5929) are median-blurred first
 (median_blur_u8, OpenCV medianBlur semantics).
@@ -34,7 +38,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ._native import COST_DEPTH_3DOF, COST_RGBD_3DOF
+from ._native import COST_DEPTH_3DOF, COST_RGBD_3DOF, PLANAR_NO_CORRESPONDENCES
 from .model import pose_matrix
 from .recognizer import (CAM_TO_BODY, K_MESH_ADDITIVE_INFLATION, CameraIntrinsics, ModelMetaData,
                          ObjectRecognizer, PerchParams, RecognitionInput, States, _dims, radius_counts)
@@ -55,7 +59,8 @@ class TableParams:
 
 def pr2_gpu_params(**kw) -> PerchParams:
     """perch_params of config/pr2_gpu_env_config.yaml (3-DoF GPU): stride 4, 7.5 mm sensor radius, 30
-    neighbours for a valid pose, colour cost with threshold 11.5, cylinder observed totals, no ICP."""
+    neighbours for a valid pose, colour cost with threshold 11.5, cylinder observed totals, icp_type 0 (the planar
+    x / y / yaw ICP, run when the search is asked for use_icp)."""
     p = PerchParams(icp_type=0, sensor_resolution=0.0075, min_neighbor_points_for_valid_pose=30, gpu_stride=4,
                     use_color_cost=True, color_distance_threshold=11.5, use_cylinder_observed=True)
     for k, v in kw.items():
@@ -155,6 +160,45 @@ def grid_states(table: TableParams, model_id: int, dims, projected_xy: np.ndarra
     return states
 
 
+def pose_in_cam_3dof(camera_pose: np.ndarray, preprocess: Sequence[np.ndarray], model: np.ndarray,
+                     xyzy: np.ndarray) -> np.ndarray:
+    """The search poses (N x 16 mat4x4, scaled by 100) of 3-DoF states (x y z yaw) in the camera, vectorised: yaw
+    quaternions with math.sin / math.cos per state, as yaw_pose_matrix; index-order 4x4 products
+    (model.chain_matmul_batch)."""
+    from .model import chain_matmul_batch, init_from_eigen_batch, pose_matrix_batch
+    cam_matrix = np.linalg.inv(camera_pose @ CAM_TO_BODY)
+    xyzy = np.asarray(xyzy, np.float64).reshape(-1, 4)
+    if not len(xyzy):
+        return init_from_eigen_batch(np.zeros((0, 4, 4)), 100)
+    yaws = [normalize_angle_positive(float(y)) for y in xyzy[:, 3]]
+    q = np.array([(0.0, 0.0, math.sin(y / 2.0), math.cos(y / 2.0)) for y in yaws])
+    mats = chain_matmul_batch(cam_matrix, pose_matrix_batch(xyzy[:, :3], q), np.stack(preprocess)[np.asarray(model)])
+    return init_from_eigen_batch(mats, 100)
+
+
+def planar_adjusted_states(states: np.ndarray, xform: np.ndarray, status: np.ndarray) -> np.ndarray:
+    """GetICPAdjustedPose's pose update for use_external_pose_list == 0 (search_env.cpp:6341-6358) of 3-DoF states
+    (N x 4: x y z yaw) by planar ICP transforms (N x 4: c s tx ty, pcore_icp_planar): the transform as a float
+    Matrix4f, vec_out = T * (x, y, z, 1) in float (each row left to right), yaw2 = atan2(T(1,0), T(0,0)), total_yaw =
+    atan2(sin(yaw1 + yaw2), cos(yaw1 + yaw2)) in double, ContPose(vec_out, 0, 0, total_yaw) -- whose constructor
+    normalises the yaw into [0, 2 pi).  A pose whose ICP found no correspondences or whose render was empty (status 4,
+    5) stays as it was, as the reference keeps pose_in when PCL does not converge."""
+    st = np.asarray(states, np.float64).reshape(-1, 4)
+    xf = np.asarray(xform, np.float64).reshape(-1, 4)
+    status = np.asarray(status).reshape(-1)
+    c, s, tx, ty = (xf[:, k].astype(np.float32) for k in range(4))
+    x, y = st[:, 0].astype(np.float32), st[:, 1].astype(np.float32)
+    zero = np.float32(0.0)
+    z = st[:, 2].astype(np.float32)
+    xo = ((c * x + (-s) * y) + zero * z) + tx
+    yo = ((s * x + c * y) + zero * z) + ty
+    tot = st[:, 3] + np.arctan2(s.astype(np.float64), c.astype(np.float64))
+    two_pi = 2.0 * math.pi
+    yaw = np.fmod(np.fmod(np.arctan2(np.sin(tot), np.cos(tot)), two_pi) + two_pi, two_pi)  # normalize_angle_positive
+    adj = np.stack([xo.astype(np.float64), yo.astype(np.float64), z.astype(np.float64), yaw], 1)
+    return np.where((status < PLANAR_NO_CORRESPONDENCES)[:, None], adj, st)
+
+
 class TabletopRecognizer(ObjectRecognizer):
     """ObjectRecognizer in the 3-DoF GPU mode (use_external_pose_list = 0)."""
 
@@ -236,24 +280,34 @@ class TabletopRecognizer(ObjectRecognizer):
         return torch.from_numpy(self._pose_in_cam(states)).to(self.device)
 
     def _pose_in_cam(self, states) -> np.ndarray:
-        """The 3-DoF states' poses in the camera, vectorised (yaw quaternions with math.sin / math.cos per
-        state, as yaw_pose_matrix; index-order 4x4 products, model.chain_matmul_batch)."""
-        from .model import chain_matmul_batch, init_from_eigen_batch, pose_matrix_batch
-        cam_matrix = np.linalg.inv(self.camera_pose @ CAM_TO_BODY)
-        if not len(states):
-            return init_from_eigen_batch(np.zeros((0, 4, 4)), 100)
-        xyzy = states.pose
-        yaws = [normalize_angle_positive(float(y)) for y in xyzy[:, 3]]
-        q = np.array([(0.0, 0.0, math.sin(y / 2.0), math.cos(y / 2.0)) for y in yaws])
-        mats = chain_matmul_batch(cam_matrix, pose_matrix_batch(xyzy[:, :3], q), np.stack(self.preprocess)[states.model])
-        return init_from_eigen_batch(mats, 100)
+        """The 3-DoF states' poses in the camera (pose_in_cam_3dof)."""
+        return pose_in_cam_3dof(self.camera_pose, self.preprocess, states.model, states.pose)
+
+    def _planar_refine(self, states, poses, pm):
+        """GetICPAdjustedPosesCPU's place between the two GPU passes (search_env.cpp:1198-1299): planar ICP of every
+        state's rendered cloud onto the observation on the device, GetICPAdjustedPose's pose update on the host, and
+        the adjusted states' poses rebuilt by _pose_in_cam.  The seconds are the planar stage's (EnvStats.icp_time)."""
+        p = self.params
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        xform, _, status, _ = self.core.icp_planar(
+            poses, pm, self.transform, cost_type=self._cost_type(), stride=p.gpu_stride,
+            depth_factor=p.gpu_depth_factor, occlusion_threshold=p.gpu_occlusion_threshold,
+            max_iterations=p.max_icp_iterations, max_correspondence=p.icp_max_correspondence)
+        t1.record()
+        adj = planar_adjusted_states(states.pose, xform.cpu().numpy(), status.cpu().numpy())
+        self.last_planar = (xform, status)
+        states = States(states.model, states.req, adj)
+        return states, self._poses_device(states), t0.elapsed_time(t1) * 1e-3
 
     def localize(self, model_names: Sequence[str], depth: np.ndarray, camera_pose: np.ndarray,
-                 depth_factor: float, rgb: Optional[np.ndarray] = None):
-        """LocalizeObjectsGreedyRender in 3-DoF mode: (model, cost, index, ContPose x y z qx qy qz qw)."""
+                 depth_factor: float, rgb: Optional[np.ndarray] = None, use_icp: int = 0):
+        """LocalizeObjectsGreedyRender in 3-DoF mode: (model, cost, index, ContPose x y z qx qy qz qw).  use_icp = 1
+        (with params.icp_type 0) refines every grid state by planar ICP before it is scored, and the ContPose is the
+        adjusted state's."""
         if not self.models or self.model_names != list(model_names):
             self.set_static_input(model_names, six_dof=False)
         self.set_input_3dof(depth, camera_pose, depth_factor, rgb)
         inp = RecognitionInput(list(model_names), depth, np.zeros_like(depth, np.uint8), depth_factor=depth_factor,
-                               camera_pose=camera_pose, use_external_pose_list=0, use_icp=0)
+                               camera_pose=camera_pose, use_external_pose_list=0, use_icp=int(use_icp))
         return self.compute_greedy_render_poses(inp)

@@ -4,6 +4,8 @@ multi-GPU configs).  Prints one JSON line per config.  Not the driver's bench (b
 
   C1  1 mesh, 128 3-DoF table-top poses, render + GICP + re-render + score (cost type 0), 640x480 -- the GPU
       side of the workload bench.py's cpu_reference_path times on the reference's CPU/OMP path
+  c1_planar  C1's scene and grid scaled to 20,000 states: the planar (x, y, yaw) ICP stage, the two-pass 3-DoF search
+      and GICP on the same states (not in the default list: --configs c1_planar)
   C2  1 mesh, 10k poses, render + score, 640x480
   C3  5 objects, 50k poses, render + GICP + re-render + score, 640x480 (+ argmin vs GT)
   C4  21 objects, 200k poses over 8 GPUs -> 25k poses per GPU, render + score
@@ -152,6 +154,105 @@ def run_c1(steps, warmup, stride=4):
                       "observed_points": int(xyz.shape[0])}), flush=True)
 
 
+def run_c1_planar(nxy=50, stride=4, runs=5, host_poses=16):
+    """c1_planar: C1's table-top scene and grid scaled to nxy x nxy x 8 states (20,000), refined by the planar
+    (x, y, yaw) ICP.  Reports the planar stage alone (PoseCore.icp_planar), the two-pass search (planar ICP, the host
+    pose update and pose rebuild, stage COST with the selection) and, as the yardstick, the only refinement the library
+    had for these states before: evaluate_icp (GICP) at 3-DoF on the same context -- `runs` alternating runs each,
+    medians.  For context also the numpy restatement of the spec (tests/icp2d_reference.py) on host_poses poses, one
+    thread each, in the place of the reference's OpenMP loop."""
+    from perception_amd.core import PoseCore
+    from perception_amd.model import compute_proj
+    from perception_amd.recognizer import preprocessing_transform
+    from perception_amd.tabletop import planar_adjusted_states, pose_in_cam_3dof
+    dev = torch.device("cuda", 0)
+    bank = syn.model_bank(["003_cracker_box"])
+    pre = [preprocessing_transform(bank.models[0], six_dof=False)]
+    core = PoseCore(0)
+    core.upload_meshes(bank.tris, bank.tris_model_count)
+    cam = syn.CAM_640
+    W, H = cam["width"], cam["height"]
+    core.set_camera(W, H, cam["fx"], cam["fy"], cam["cx"], cam["cy"],
+                    compute_proj(cam["fx"], cam["fy"], cam["cx"], cam["cy"], W, H))
+    core.set_observation(torch.zeros((H, W), dtype=torch.int32, device=dev), None,
+                         torch.zeros((0, 3), dtype=torch.float32, device=dev), None, 0.01)
+    c1 = workloads.c1_tabletop(workloads.gpu_render_fn(core, dev))
+    sc = c1.scene
+    xyz, _ = core.observed_cloud_bounded(torch.from_numpy(sc.depth_raw).to(dev), stride, sc.depth_factor)
+    core.set_observation(torch.from_numpy(c1.src_depth_cm).to(dev), None, xyz, None, 0.0075)
+    # C1's 4 x 4 cells of 4 cm around the ground truth, cut into nxy x nxy positions; its 8 yaws
+    gx, gy = 0.60, -0.04
+    xs = gx - 0.08 + 0.16 * (np.arange(nxy) + 0.5) / nxy
+    ys = gy - 0.08 + 0.16 * (np.arange(nxy) + 0.5) / nxy
+    X, Y, K = np.meshgrid(xs, ys, np.arange(8), indexing="ij")
+    states = np.stack([X.ravel(), Y.ravel(), np.full(X.size, sc.table_height), K.ravel() * np.pi / 4], 1)
+    n = len(states)
+    model0 = np.zeros(n, np.int32)
+    M = (sc.camera_pose @ syn.CAM_TO_BODY).astype(np.float32)
+    poses = torch.from_numpy(pose_in_cam_3dof(sc.camera_pose, pre, model0, states)).to(dev)
+    pm = torch.zeros(n, dtype=torch.int32, device=dev)
+    tot = torch.full((n,), float(xyz.shape[0]), dtype=torch.float32, device=dev)
+    keys = torch.full((1,), PCORE_KEY_NONE, dtype=torch.int64, device=dev)
+    out_p = None
+
+    def planar():
+        nonlocal out_p
+        out_p = core.icp_planar(poses, pm, M, stride=stride, out=out_p)
+
+    def two_pass():
+        planar()
+        adj = planar_adjusted_states(states, out_p[0].cpu().numpy(), out_p[2].cpu().numpy())
+        p2 = torch.from_numpy(pose_in_cam_3dof(sc.camera_pose, pre, model0, adj)).to(dev)
+        keys.fill_(PCORE_KEY_NONE)
+        core.evaluate(p2, pm, None, tot, cost_type=0, stride=stride, sensor_resolution=0.0075, select=(keys, 0, 1))
+
+    def gicp():
+        core.evaluate_icp(poses, pm, None, tot, cost_type=0, stride=stride, sensor_resolution=0.0075)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for fn in (planar, two_pass, gicp):  # warm-up: scratch, grids, target covariances
+        once(fn)
+    t = {"planar": [], "two_pass": [], "gicp": []}
+    gicp_stage = []
+    for _ in range(runs):  # alternating
+        t["planar"].append(once(planar))
+        t["gicp"].append(once(gicp))
+        gicp_stage.append(float(core.stats()["icp_runtime"]))
+        t["two_pass"].append(once(two_pass))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    status = out_p[2].cpu().numpy()
+    iters = out_p[1].cpu().numpy()
+    res = {"config": "c1_planar", "poses": n, "width": W, "height": H, "stride": stride,
+           "observed_points": int(xyz.shape[0]), "runs": runs,
+           "planar_s": med["planar"], "planar_poses_per_s": n / med["planar"],
+           "two_pass_s": med["two_pass"], "two_pass_poses_per_s": n / med["two_pass"],
+           "gicp_call_s": med["gicp"], "gicp_call_poses_per_s": n / med["gicp"],
+           "gicp_stage_s": float(np.median(gicp_stage)),
+           "planar_s_all": t["planar"], "gicp_call_s_all": t["gicp"], "two_pass_s_all": t["two_pass"],
+           "status_counts": [int(v) for v in np.bincount(status, minlength=6)],
+           "iters_mean": float(iters.mean()), "iters_at_cap": int((iters >= 20).sum())}
+    if host_poses > 0:
+        from tests import icp2d_reference as ref
+        zb = core.render(poses[:host_poses].contiguous(), pm[:host_poses].contiguous(), None).cpu().numpy()
+        import oracle
+        pts, pidx, _ = oracle.depth_to_cloud(zb, stride, sc.cx, sc.cy, sc.fx, sc.fy, 100.0)
+        clouds = [pts[pidx == i] for i in range(host_poses)]
+        obs = xyz.cpu().numpy()
+        t0 = time.perf_counter()
+        h = ref.run_poses(clouds, obs, M, threads=16)
+        dt = time.perf_counter() - t0
+        same = bool(np.array_equal(h[0].view(np.uint64), out_p[0][:host_poses].cpu().numpy().view(np.uint64)))
+        res.update({"host_numpy_poses": host_poses, "host_numpy_threads": 16, "host_numpy_s": dt,
+                    "host_numpy_poses_per_s": host_poses / dt, "host_numpy_bit_equal": same})
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4,C5")
@@ -163,6 +264,8 @@ def main():
     sc = a.scale
     if "C1" in sel:
         run_c1(max(a.steps, 10), max(a.warmup, 2))
+    if "c1_planar" in sel:
+        run_c1_planar(nxy=max(2, int(round(50 * sc ** 0.5))))
     if "C2" in sel:
         run("C2", ["003_cracker_box"], int(10000 * sc), syn.CAM_640, False, a.steps, a.warmup)
     if "C3" in sel:
