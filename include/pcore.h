@@ -219,6 +219,47 @@ int pcore_icp_planar(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose
  * sum qy tx, sum qy ty, sum d^2 -- into d_out (n x 4: c', s', tx', ty'), one thread each. */
 int pcore_debug_planar_step(const double* d_sums, double* d_out, int32_t n, pcore_stream stream);
 
+/* Point-to-plane ICP against a projective scene (cuda_icp: ICP_Point2Plane_cuda, icp.cu:157-218; Scene_projective,
+ * depth_scene.h; get_normal, scene/common.cpp:17-107).  A correspondence is one projection and one gather from the
+ * observed depth image: no neighbour search, no labels, no covariances.  The loop is the reference's, operation for
+ * operation, with three build-owned choices (sum order, trigonometry, float-to-pixel conversion): DESIGN.md section 5,
+ * "Point-to-plane ICP spec". */
+typedef struct pcore_p2p_icp_params {
+    int32_t max_iterations;     /* 30   (ICPConvergenceCriteria, icp.h:39-51) */
+    float   relative_fitness;   /* 1e-5 */
+    float   relative_rmse;      /* 1e-5 */
+    float   max_dist_diff;      /* 0.1 m (Scene_projective, depth_scene.h:9) */
+} pcore_p2p_icp_params;
+
+/* Scene_projective's buffers of a depth image (int32 cm, read as uint32 for the points and saturated to uint16 for the
+ * normals): d_out_pcd and d_out_normal, H x W x 3 floats each -- dep2pcd of every pixel, and the linemod normal (radius
+ * 5, depth below 2000, difference threshold 50) where it is defined, zero elsewhere.  Needs only a context; the camera
+ * is the arguments'. */
+int pcore_scene_projective(pcore_ctx* ctx, const int32_t* d_depth_cm, int32_t width, int32_t height, float fx, float fy,
+                           float cx, float cy, float* d_out_pcd, float* d_out_normal, pcore_stream stream);
+
+/* Render every pose at stage CLOUD (stride samples; with d_pose_label the 6-DoF source occlusion of
+ * pcore_evaluate_icp, with NULL the 3-DoF one) and align each cloud to the scene of the observation's source depth.
+ * d_out_T: N x 16 row-major, the cumulative camera-frame transform; d_out_fitness: accepted points / points;
+ * d_out_rmse: sqrt(sum of squared plane distances / accepted); d_out_iters: the iteration at which the loop returned
+ * (an empty render: T = I, fitness 0, rmse 0, iteration 0); d_out_poses (nullable, N x 16): concatenate_transforms(T,
+ * pose), the pose pcore_evaluate re-scores.  All cost types are accepted.  Every argument is checked before the first
+ * launch.  The batch is split into equal chunks that fit a scratch budget of min(32 GiB, 40 % of the free device
+ * memory) at 16 B per pose and stride sample.  The scene (32 B per pixel) is built on first use and kept while the
+ * observation and the camera stay the same; a capturing stream that would need that build, or new scratch, gets
+ * PCORE_E_STATE (run the call once before the capture). */
+int pcore_icp_point2plane(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_model,
+                          const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* params,
+                          const pcore_p2p_icp_params* icp, float* d_out_T, float* d_out_fitness, float* d_out_rmse,
+                          int32_t* d_out_iters, float* d_out_poses, pcore_stream stream);
+
+/* Test hook (no reference counterpart): the same kernel over caller-made slots (segment i: d_xyzw + 4 i seg_stride,
+ * d_seg_cnt[i] points of 4 floats, moved in place) and a caller-made scene (one float4 per pixel each). */
+int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_t seg_stride, int32_t num_segs,
+                           const float* d_scene_pcd4, const float* d_scene_normal4, int32_t width, int32_t height,
+                           float fx, float fy, float cx, float cy, const pcore_p2p_icp_params* icp, float* d_out_T,
+                           float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream);
+
 /* Stage "RENDER" / "DEBUG" images (renderer.cu:1594-1615): full-resolution int32 z-buffers (cm) with source
  * occlusion and INT_MAX -> 0 (image_render, image_renderer.cuh:336-496).  d_out_depth: N x H x W.
  * d_out_color (nullable): the reference's result_color -- three planes red, green, blue of N x H x W uint8 each,

@@ -33,7 +33,10 @@ EXPORTED_SYMBOLS = (
     "pcore_count_within", "pcore_state_poses", "pcore_evaluate_select", "pcore_get_tile_info", "pcore_debug_lm_solve",
     "pcore_debug_covariances", "pcore_debug_covariances_cloud", "pcore_debug_gicp_help_stats", "pcore_depth_to_cloud_ex",
     "pcore_icp_planar", "pcore_debug_planar_step",
+    "pcore_scene_projective",
 )
+# declared in include/pcore.h too; kept apart because tests/test_abi.py's symbol pattern stops at a digit
+EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds")
 
 
 class PcoreError(RuntimeError):
@@ -83,6 +86,18 @@ class PlanarIcpParams(ctypes.Structure):
     _fields_ = [("max_iterations", ctypes.c_int32), ("max_correspondence", ctypes.c_float),
                 ("transformation_epsilon", ctypes.c_double), ("fitness_epsilon", ctypes.c_double)]
 
+
+class P2pIcpParams(ctypes.Structure):
+    """pcore_p2p_icp_params (include/pcore.h)."""
+    _fields_ = [("max_iterations", ctypes.c_int32), ("relative_fitness", ctypes.c_float),
+                ("relative_rmse", ctypes.c_float), ("max_dist_diff", ctypes.c_float)]
+
+
+# ICPConvergenceCriteria (cuda_icp icp.h:39-51) and Scene_projective's max_dist_diff (depth_scene.h:9)
+P2P_MAX_ITER = 30
+P2P_REL_FITNESS = 1e-5
+P2P_REL_RMSE = 1e-5
+P2P_MAX_DIST_DIFF = 0.1
 
 # GetICPAdjustedPose's settings (search_env.cpp:6235-6396; env_config.yaml max_icp_iterations, icp_max_correspondence)
 PLANAR_MAX_ITER = 20
@@ -165,6 +180,12 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                        ctypes.POINTER(PlanarIcpParams), vp, vp, vp, vp, vp]
     if hasattr(L, "pcore_debug_planar_step"):
         L.pcore_debug_planar_step.argtypes = [vp, vp, i32, vp]
+    if hasattr(L, "pcore_icp_point2plane"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_scene_projective.argtypes = [vp, vp, i32, i32, f32, f32, f32, f32, vp, vp, vp]
+        L.pcore_icp_point2plane.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(EvalParams),
+                                            ctypes.POINTER(P2pIcpParams), vp, vp, vp, vp, vp, vp]
+        L.pcore_debug_p2p_clouds.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, f32, f32, f32, f32,
+                                             ctypes.POINTER(P2pIcpParams), vp, vp, vp, vp, vp]
     L.pcore_select.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp]
     L.pcore_pose_distances.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.pcore_set_observation_colors.argtypes = [vp, vp, i32, vp]
@@ -175,7 +196,7 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                         vp, vp]
     L.pcore_count_within.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     L.pcore_state_poses.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double), vp, i32, i32, vp, vp]
-    for name in EXPORTED_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + EXPORTED_SYMBOLS_WITH_DIGITS:
         if name not in ("pcore_destroy", "pcore_last_error", "pcore_generation") and hasattr(L, name):
             getattr(L, name).restype = ctypes.c_int
     L.pcore_generation.restype = ctypes.c_uint64

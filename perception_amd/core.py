@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _native
-from ._native import Camera, EvalParams, IcpParams, PcoreError, PlanarIcpParams
+from ._native import Camera, EvalParams, IcpParams, P2pIcpParams, PcoreError, PlanarIcpParams
 
 
 def _ptr(t: Optional[torch.Tensor], dtype: torch.dtype, name: str):
@@ -279,6 +279,92 @@ class PoseCore:
         if rc != _native.PCORE_OK:
             raise PcoreError(rc, "pcore_debug_planar_step failed")
         return out
+
+    def scene_projective(self, depth_cm: torch.Tensor, fx: float, fy: float, cx: float, cy: float, stream=None
+                         ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """pcore_scene_projective: the reference's Scene_projective buffers of an (H, W) int32 cm depth image ->
+        (points (H, W, 3) float32, linemod normals (H, W, 3) float32) on the GPU."""
+        h, w = depth_cm.shape[-2:]
+        pcd = torch.empty((h, w, 3), dtype=torch.float32, device=depth_cm.device)
+        nrm = torch.empty((h, w, 3), dtype=torch.float32, device=depth_cm.device)
+        self._check(self.lib.pcore_scene_projective(
+            self._h, _ptr(depth_cm, torch.int32, "depth_cm"), int(w), int(h), float(fx), float(fy), float(cx),
+            float(cy), _ptr(pcd, torch.float32, "pcd"), _ptr(nrm, torch.float32, "normal"), _stream(stream)))
+        return pcd, nrm
+
+    def icp_point2plane(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor] = None,
+                        cost_type: int = _native.COST_DEPTH_6DOF, stride: int = 8, depth_factor: float = 100.0,
+                        occlusion_threshold: float = 1.0, max_iterations: int = _native.P2P_MAX_ITER,
+                        relative_fitness: float = _native.P2P_REL_FITNESS,
+                        relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
+                        out=None, out_poses: Optional[torch.Tensor] = None, stream=None):
+        """Point-to-plane ICP of every pose's rendered stride-sample cloud against the projective scene of the
+        observation's source depth (pcore_icp_point2plane); pose_label selects the 6-DoF source occlusion, None the
+        3-DoF one.  Returns (T (N, 16) float32, fitness (N,), rmse (N,), iterations (N,) int32) on the GPU; with
+        out_poses (N, 16) also writes concatenate_transforms(T, pose) there."""
+        n = int(poses.shape[0])
+        dev = poses.device
+        if out is None:
+            out = (torch.empty((n, 16), dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        T, fitness, rmse, iters = out
+        p = EvalParams(int(cost_type), 0, int(stride), float(depth_factor), 0.0, float(occlusion_threshold), 0.0)
+        ip = P2pIcpParams(int(max_iterations), float(relative_fitness), float(relative_rmse), float(max_dist_diff))
+        self._check(self.lib.pcore_icp_point2plane(
+            self._h, _ptr(poses, torch.float32, "poses"), _ptr(pose_model, torch.int32, "pose_model"),
+            _ptr(pose_label, torch.int32, "pose_label"), n, ctypes.byref(p), ctypes.byref(ip),
+            _ptr(T, torch.float32, "T"), _ptr(fitness, torch.float32, "fitness"), _ptr(rmse, torch.float32, "rmse"),
+            _ptr(iters, torch.int32, "iterations"), _ptr(out_poses, torch.float32, "out_poses"), _stream(stream)))
+        return T, fitness, rmse, iters
+
+    def p2p_clouds(self, xyzw: torch.Tensor, seg_cnt: torch.Tensor, scene_pcd4: torch.Tensor,
+                   scene_normal4: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
+                   max_iterations: int = _native.P2P_MAX_ITER, relative_fitness: float = _native.P2P_REL_FITNESS,
+                   relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
+                   stream=None):
+        """pcore_debug_p2p_clouds: the point-to-plane ICP kernel over caller-made slots xyzw (S, cap, 4) float32 with
+        seg_cnt (S,) int32 points each (moved in place) and a caller-made scene (H, W, 4) + (H, W, 4).  Returns (T
+        (S, 16), fitness, rmse, iterations)."""
+        s, cap = int(xyzw.shape[0]), int(xyzw.shape[1])
+        h, w = int(scene_pcd4.shape[0]), int(scene_pcd4.shape[1])
+        dev = xyzw.device
+        T = torch.empty((s, 16), dtype=torch.float32, device=dev)
+        fitness = torch.empty(s, dtype=torch.float32, device=dev)
+        rmse = torch.empty(s, dtype=torch.float32, device=dev)
+        iters = torch.empty(s, dtype=torch.int32, device=dev)
+        ip = P2pIcpParams(int(max_iterations), float(relative_fitness), float(relative_rmse), float(max_dist_diff))
+        rc = self.lib.pcore_debug_p2p_clouds(
+            _ptr(xyzw, torch.float32, "xyzw"), _ptr(seg_cnt, torch.int32, "seg_cnt"), cap, s,
+            _ptr(scene_pcd4, torch.float32, "scene_pcd4"), _ptr(scene_normal4, torch.float32, "scene_normal4"), w, h,
+            float(fx), float(fy), float(cx), float(cy), ctypes.byref(ip), _ptr(T, torch.float32, "T"),
+            _ptr(fitness, torch.float32, "fitness"), _ptr(rmse, torch.float32, "rmse"),
+            _ptr(iters, torch.int32, "iterations"), _stream(stream))
+        if rc != _native.PCORE_OK:
+            raise PcoreError(rc, "pcore_debug_p2p_clouds failed")
+        return T, fitness, rmse, iters
+
+    def evaluate_p2p(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
+                     pose_obs_total: Optional[torch.Tensor], cost_type: int = _native.COST_DEPTH_6DOF,
+                     calc_obs_cost: bool = True, stride: int = 8, depth_factor: float = 100.0,
+                     sensor_resolution: float = 0.01, occlusion_threshold: float = 1.0,
+                     max_iterations: int = _native.P2P_MAX_ITER, relative_fitness: float = _native.P2P_REL_FITNESS,
+                     relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
+                     color_distance_threshold: float = 15.0, stream=None):
+        """Stage COST with the point-to-plane ICP in GICP's place: icp_point2plane with out_poses, then evaluate on the
+        adjusted poses.  Returns (adjusted poses (N, 16), iterations (N,), rc, oc, diff, fitness, rmse)."""
+        n = int(poses.shape[0])
+        adj = torch.empty((n, 16), dtype=torch.float32, device=poses.device)
+        label = pose_label if cost_type == _native.COST_DEPTH_6DOF else None
+        _, fitness, rmse, iters = self.icp_point2plane(
+            poses, pose_model, label, cost_type=cost_type, stride=stride, depth_factor=depth_factor,
+            occlusion_threshold=occlusion_threshold, max_iterations=max_iterations,
+            relative_fitness=relative_fitness, relative_rmse=relative_rmse, max_dist_diff=max_dist_diff,
+            out_poses=adj, stream=stream)
+        rc, oc, df = self.evaluate(adj, pose_model, pose_label, pose_obs_total, cost_type=cost_type,
+                                   calc_obs_cost=calc_obs_cost, stride=stride, depth_factor=depth_factor,
+                                   sensor_resolution=sensor_resolution, occlusion_threshold=occlusion_threshold,
+                                   color_distance_threshold=color_distance_threshold, stream=stream)
+        return adj, iters, rc, oc, df, fitness, rmse
 
     def render(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
                occlusion_threshold: float = 1.0, out: Optional[torch.Tensor] = None, color: bool = False,

@@ -7,6 +7,7 @@
 #include "pcore_streams.h"
 #include "pcore_gicp_math.h"
 #include "pcore_icp2d_math.h"
+#include "pcore_p2p_math.h"
 
 #include <algorithm>
 #include <climits>
@@ -134,6 +135,11 @@ struct pcore_ctx {
     LabelGrid planar_grid{};
     DevBuf<int32_t> planar_cell_start;
     DevBuf<float4> planar_pts;
+    // point-to-plane ICP (pcore_icp_point2plane): the projective scene of src_depth (a float4 point and a float4 normal
+    // per pixel), built on first use and kept while the observation and the camera stay the same
+    uint64_t p2p_obs_serial = 0;      // the observation the scene below was built from (0: none)
+    pcore_camera p2p_cam{};
+    DevBuf<float4> p2p_pcd, p2p_normal;
 };
 
 namespace {
@@ -340,6 +346,7 @@ void pcore_destroy(pcore_ctx* c) {
     (void)dev_free(c->stri_orig); (void)dev_free(c->tri_lab); (void)dev_free(c->obs_lab); (void)dev_free(c->colour_id);
     (void)dev_free(c->metric_part); (void)dev_free(c->tri_rgb); (void)dev_free(c->render_tri);
     (void)dev_free(c->planar_cell_start); (void)dev_free(c->planar_pts);
+    (void)dev_free(c->p2p_pcd); (void)dev_free(c->p2p_normal);
     for (hipEvent_t e : c->icp_ev) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1289,6 +1296,179 @@ int pcore_icp_planar(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_m
 int pcore_debug_planar_step(const double* d_sums, double* d_out, int32_t n, pcore_stream stream) {
     if (n < 0 || (n > 0 && (!d_sums || !d_out))) return PCORE_E_INVALID_ARG;
     return launch_planar_step_test(d_sums, d_out, n, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
+}
+
+int pcore_scene_projective(pcore_ctx* c, const int32_t* d_depth_cm, int32_t width, int32_t height, float fx, float fy,
+                           float cx, float cy, float* d_out_pcd, float* d_out_normal, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (width <= 0 || height <= 0 || width > 16384 || height > 16384)
+        return fail(c, PCORE_E_INVALID_ARG, "scene_projective: bad image size");
+    if (!d_depth_cm || !d_out_pcd || !d_out_normal)
+        return fail(c, PCORE_E_INVALID_ARG, "scene_projective: null pointer");
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, launch_p2p_scene(d_depth_cm, width, height, fx, fy, cx, cy, nullptr, nullptr, d_out_pcd, d_out_normal,
+                             (hipStream_t)stream));
+    return PCORE_OK;
+}
+
+namespace {
+
+// pcore_p2p_icp_params' checks; nullptr when they hold
+const char* p2p_params_error(const pcore_p2p_icp_params* ip) {
+    if (ip->max_iterations < 0) return "max_iterations must be >= 0";
+    if (std::isnan(ip->relative_fitness) || ip->relative_fitness < 0.0f) return "relative_fitness must be >= 0";
+    if (std::isnan(ip->relative_rmse) || ip->relative_rmse < 0.0f) return "relative_rmse must be >= 0";
+    if (std::isnan(ip->max_dist_diff) || ip->max_dist_diff < 0.0f) return "max_dist_diff must be >= 0";
+    return nullptr;
+}
+
+}  // namespace
+
+// Point-to-plane ICP against the projective scene of the observation's source depth (ICP_Point2Plane_cuda,
+// cuda_icp/icp.cu:157-218): stage CLOUD into per-pose slots (launch_render_cloud, as pcore_evaluate_icp's first step),
+// then p2p_icp_kernel over the slots.  Every check comes before the first launch, so an invalid call writes nothing.
+int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
+                          int32_t num_poses, const pcore_eval_params* p, const pcore_p2p_icp_params* ip,
+                          float* d_out_T, float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters,
+                          float* d_out_poses, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (!p || !ip) return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: null parameters");
+    if (!c->have_mesh || !c->have_cam || !c->have_obs)
+        return fail(c, PCORE_E_STATE, "icp_point2plane: meshes, camera and observation must be set first");
+    if (p->cost_type != PCORE_COST_DEPTH_3DOF && p->cost_type != PCORE_COST_DEPTH_6DOF &&
+        p->cost_type != PCORE_COST_RGBD_3DOF)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: unknown cost_type");
+    if (const char* e = p2p_params_error(ip)) return fail(c, PCORE_E_INVALID_ARG, std::string("icp_point2plane: ") + e);
+    if (num_poses < 0 || (num_poses > 0 && (!d_poses || !d_pose_model || !d_out_T || !d_out_fitness || !d_out_rmse ||
+                                            !d_out_iters)))
+        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: null pose / output pointer");
+    if (d_pose_label && !c->obs_has_mask)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: pose labels need a source mask");
+    const int W = c->cam.width, H = c->cam.height;
+    if (p->stride <= 0 || W % p->stride != 0)
+        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: width must be a multiple of stride");
+    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
+    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: sampled image too large");
+    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
+        return fail(c, PCORE_E_INVALID_ARG,
+                    "icp_point2plane: sampled z-buffer does not fit in LDS (use a larger stride)");
+    if (num_poses == 0) return PCORE_OK;
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nsamp = ws * hs;
+    // chunks by the scratch budget, as pcore_icp_planar: a slot of nsamp points (16 B) and a count per pose, at most
+    // min(32 GiB, 40 % of the free device memory); PCORE_P2P_SCRATCH_BYTES sets the budget (test / A/B knob)
+    const size_t per_pose = (size_t)nsamp * sizeof(float4) + sizeof(int32_t);
+    size_t budget = (size_t)32 << 30;
+    {
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+            budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
+    }
+    if (const char* e = getenv("PCORE_P2P_SCRATCH_BYTES")) budget = (size_t)std::max(1LL, atoll(e));
+    const int max_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_pose), 0x7fffffff);
+    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
+    const int chunk = (num_poses + nchunks - 1) / nchunks;
+    // what has to be built or allocated first; none of it may happen while the stream captures
+    const pcore_camera& cam = c->cam;
+    const bool scene_stale = c->p2p_obs_serial != c->obs_serial || c->p2p_cam.width != W || c->p2p_cam.height != H ||
+                             std::memcmp(&c->p2p_cam.fx, &cam.fx, sizeof(float)) != 0 ||
+                             std::memcmp(&c->p2p_cam.fy, &cam.fy, sizeof(float)) != 0 ||
+                             std::memcmp(&c->p2p_cam.cx, &cam.cx, sizeof(float)) != 0 ||
+                             std::memcmp(&c->p2p_cam.cy, &cam.cy, sizeof(float)) != 0;
+    const bool setup = scene_stale || c->sampled_stride != p->stride || !c->icp_cloud.p || !c->icp_count.p ||
+                       c->icp_cloud.n < (size_t)chunk * nsamp || c->icp_count.n < (size_t)chunk;
+    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap_status) != hipSuccess) {
+        (void)hipGetLastError();
+        cap_status = hipStreamCaptureStatusActive;
+    }
+    if (setup && cap_status != hipStreamCaptureStatusNone)
+        return fail(c, PCORE_E_STATE, "icp_point2plane: the scene or the scratch would have to be built while the "
+                                      "stream captures; run the call once before the capture");
+    if (scene_stale) {
+        const size_t npx = (size_t)W * H;
+        HIPC(c, hipStreamSynchronize(s));  // an earlier call on the stream may still read the old scene
+        c->p2p_obs_serial = 0;
+        c->generation++;
+        HIPC(c, dev_reserve(c->p2p_pcd, npx));
+        HIPC(c, dev_reserve(c->p2p_normal, npx));
+        HIPC(c, launch_p2p_scene(c->src_depth.p, W, H, cam.fx, cam.fy, cam.cx, cam.cy, c->p2p_pcd.p, c->p2p_normal.p,
+                                 nullptr, nullptr, s));
+        c->p2p_cam = cam;
+        c->p2p_obs_serial = c->obs_serial;
+    }
+    int rc = ensure_sampled(c, p->stride, s);
+    if (rc != PCORE_OK) return rc;
+    HIPC(c, reserve_gen(c, c->icp_cloud, (size_t)chunk * nsamp));
+    HIPC(c, reserve_gen(c, c->icp_count, (size_t)chunk));
+    FusedArgs a{};
+    fill_fused_args(c, p, a);
+    P2pArgs g{};
+    g.src = c->icp_cloud.p;
+    g.src_count = c->icp_count.p;
+    g.src_cap = nsamp;
+    g.scene_pcd = c->p2p_pcd.p;
+    g.scene_normal = c->p2p_normal.p;
+    g.width = W;
+    g.height = H;
+    g.fx = cam.fx; g.fy = cam.fy; g.cx = cam.cx; g.cy = cam.cy;
+    g.max_dist_diff = ip->max_dist_diff;
+    g.rel_fitness = ip->relative_fitness;
+    g.rel_rmse = ip->relative_rmse;
+    g.max_iter = ip->max_iterations;
+    g.poses_in = d_poses;
+    g.poses_out = d_out_poses;
+    g.out_T = d_out_T;
+    g.out_fitness = d_out_fitness;
+    g.out_rmse = d_out_rmse;
+    g.out_iters = d_out_iters;
+    for (int base = 0; base < num_poses; base += chunk) {
+        const int n = std::min(chunk, num_poses - base);
+        a.poses = d_poses + (size_t)16 * base;
+        a.pose_model = d_pose_model + base;
+        a.pose_label = d_pose_label ? d_pose_label + base : nullptr;
+        a.num_poses = n;
+        a.cloud_out = c->icp_cloud.p;
+        a.cloud_count = c->icp_count.p;
+        a.cloud_cap = nsamp;
+        a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
+        if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
+        if (a.tcap <= 0) a.tcap = a.ws * a.hs;
+        HIPC(c, launch_render_cloud(a, s));
+        g.pose_base = base;
+        HIPC(c, launch_p2p_icp(g, n, s));
+    }
+    return PCORE_OK;
+}
+
+int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_t seg_stride, int32_t num_segs,
+                           const float* d_scene_pcd4, const float* d_scene_normal4, int32_t width, int32_t height,
+                           float fx, float fy, float cx, float cy, const pcore_p2p_icp_params* ip, float* d_out_T,
+                           float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream) {
+    if (!ip || p2p_params_error(ip) || num_segs < 0 || seg_stride < 0 || width <= 0 || height <= 0 || width > 16384 ||
+        height > 16384 || !d_scene_pcd4 || !d_scene_normal4)
+        return PCORE_E_INVALID_ARG;
+    if (num_segs > 0 && (!d_xyzw || !d_seg_cnt || !d_out_T || !d_out_fitness || !d_out_rmse || !d_out_iters))
+        return PCORE_E_INVALID_ARG;
+    P2pArgs g{};
+    g.src = (float4*)d_xyzw;
+    g.src_count = d_seg_cnt;
+    g.src_cap = seg_stride;
+    g.scene_pcd = (const float4*)d_scene_pcd4;
+    g.scene_normal = (const float4*)d_scene_normal4;
+    g.width = width;
+    g.height = height;
+    g.fx = fx; g.fy = fy; g.cx = cx; g.cy = cy;
+    g.max_dist_diff = ip->max_dist_diff;
+    g.rel_fitness = ip->relative_fitness;
+    g.rel_rmse = ip->relative_rmse;
+    g.max_iter = ip->max_iterations;
+    g.out_T = d_out_T;
+    g.out_fitness = d_out_fitness;
+    g.out_rmse = d_out_rmse;
+    g.out_iters = d_out_iters;
+    return launch_p2p_icp(g, num_segs, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
 }
 
 int pcore_render(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,

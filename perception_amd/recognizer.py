@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import io as pio
-from ._native import COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, PCORE_KEY_NONE
+from ._native import (COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, P2P_MAX_DIST_DIFF, P2P_MAX_ITER,
+                      P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE)
 from .core import PoseCore, decode_keys
 from .distributed import allreduce_min_keys, shard_range
 from .model import (Model, chain_matmul_batch, compute_proj, init_from_eigen_batch, matmul_lazy, pose_matrix_batch,
@@ -40,7 +41,9 @@ K_MESH_ADDITIVE_INFLATION = 0.01  # object_model.cpp:43
 class PerchParams:
     """perch_params of sbpl_perception/config/pr3_env_config.yaml (6-DoF GPU settings) + defaults of
     search_env.cpp:153-188."""
-    icp_type: int = 3                        # 3 = GICP inside the GPU flow
+    # 3 = GICP inside the GPU flow; 0 = the 3-DoF planar ICP; 4 = point-to-plane projective ICP inside the GPU flow
+    # (a build extension: the reference's icp_type goes to 3; its cuda_icp library has the kernel, PoseCore.evaluate_p2p)
+    icp_type: int = 3
     sensor_resolution: float = 0.01          # sensor_resolution_radius (m)
     min_neighbor_points_for_valid_pose: int = 30
     gpu_batch_size: int = 700
@@ -63,6 +66,11 @@ class PerchParams:
     # the 3-DoF planar ICP (icp_type 0; env_config.yaml max_icp_iterations, icp_max_correspondence)
     max_icp_iterations: int = 20
     icp_max_correspondence: float = 0.05
+    # the point-to-plane ICP (icp_type 4; ICPConvergenceCriteria, cuda_icp icp.h:39-51; depth_scene.h:9)
+    p2p_max_iterations: int = P2P_MAX_ITER
+    p2p_relative_fitness: float = P2P_REL_FITNESS
+    p2p_relative_rmse: float = P2P_REL_RMSE
+    p2p_max_dist_diff: float = P2P_MAX_DIST_DIFF
 
 
 @dataclass
@@ -525,6 +533,13 @@ class ObjectRecognizer:
                                        max_iterations=p.icp_max_iterations, rotation_epsilon=p.icp_rotation_epsilon,
                                        transformation_epsilon=p.icp_transformation_epsilon,
                                        out=(adj_all, iters, rc, oc, df))
+                self.core.select(rc, oc, pm, K, index_base=lo, keys=keys)
+            elif p.icp_type == 4 and inp.use_icp:
+                adj_all, iters, rc, oc, df, _, _ = self.core.evaluate_p2p(
+                    poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride, depth_factor=p.gpu_depth_factor,
+                    sensor_resolution=p.sensor_resolution, occlusion_threshold=p.gpu_occlusion_threshold,
+                    max_iterations=p.p2p_max_iterations, relative_fitness=p.p2p_relative_fitness,
+                    relative_rmse=p.p2p_relative_rmse, max_dist_diff=p.p2p_max_dist_diff)
                 self.core.select(rc, oc, pm, K, index_base=lo, keys=keys)
             else:  # the argmin keys folded in the scoring launch (pcore_evaluate_select)
                 self.core.evaluate(poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride,

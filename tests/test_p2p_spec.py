@@ -1,0 +1,185 @@
+"""CPU: the point-to-plane ICP spec's numpy restatement (tests/p2p_reference.py) against the committed oracle
+(oracle.ref_icp, the reference's CPU path restated), and what the spec's own sum order costs.
+
+The restatement has two switches.  In index order with libm's sin / cos it must equal the oracle bit for bit: that pins
+everything but the build-owned choices (sum order, trigonometry, float-to-pixel conversion) to the oracle.  In wave
+order -- what the GPU kernel runs, tests/test_gpu_p2p.py -- the known answers hold exactly, and near the ground truth
+the result differs from the oracle's by a few one-point association flips."""
+import numpy as np
+import pytest
+
+import oracle
+from perception_amd import workloads
+from perception_amd.model import init_from_eigen_batch
+from tests import p2p_reference as ref
+from tests.helpers import oracle_render_fn
+
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def c1():
+    return workloads.c1_tabletop(oracle_render_fn)
+
+
+@pytest.fixture(scope="module")
+def scene(c1):
+    sc = c1.scene
+    return oracle.ref_scene(c1.src_depth_cm, sc.fx, sc.fy, sc.cx, sc.cy)
+
+
+def _clouds(c1, poses, stride):
+    sc = c1.scene
+    z = oracle.ref_render_cpu(sc.bank.tris, poses, sc.width, sc.height, sc.proj)
+    xyz, pidx, _ = oracle.depth_to_cloud(z, stride, sc.cx, sc.cy, sc.fx, sc.fy, 100.0)
+    return [xyz[pidx == i] for i in range(len(poses))]
+
+
+def _cam(c1):
+    sc = c1.scene
+    return sc.fx, sc.fy, sc.cx, sc.cy
+
+
+def test_library_and_header_carry_the_entry_points():
+    """The three entry points are declared in include/pcore.h, exported by the library and typed by _native."""
+    import os
+
+    from perception_amd import _native
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "pcore.h")).read()
+    lib = _native.load()
+    for name in ("pcore_scene_projective",) + _native.EXPORTED_SYMBOLS_WITH_DIGITS:
+        assert f"int {name}(" in header, name
+        assert getattr(lib, name).argtypes is not None and getattr(lib, name).restype is not None, name
+    assert lib.pcore_abi_version() == 7
+    assert "typedef struct pcore_p2p_icp_params" in header
+    import ctypes
+    assert ctypes.sizeof(_native.P2pIcpParams) == 16
+
+
+# -- 1. bitwise against the oracle in index order ---------------------------------------------------------------
+
+INDEX_CANDIDATES = (0, 10, 30, 50, 81, 115)
+
+
+def test_index_order_with_libm_is_the_oracle_bit_for_bit(c1, scene):
+    pcd, nrm = scene
+    clouds = _clouds(c1, c1.poses[list(INDEX_CANDIDATES)], 8)
+    its = []
+    for i, cloud in zip(INDEX_CANDIDATES, clouds):
+        assert len(cloud) > 64
+        T0, f0, r0, it0, moved0 = oracle.ref_icp(cloud, pcd, nrm, *_cam(c1))
+        T1, f1, r1, it1, moved1 = ref.icp(cloud, pcd, nrm, *_cam(c1), order="index", trig="libm")
+        assert it1 == it0, f"candidate {i}: iteration {it1} != {it0}"
+        assert ref.same_bits(T1, T0), f"candidate {i}: T"
+        assert ref.same_bits(f1, F(f0)) and ref.same_bits(r1, F(r0)), f"candidate {i}: fitness / rmse"
+        assert ref.same_bits(moved1, moved0), f"candidate {i}: moved cloud"
+        its.append(it0)
+    # both exits and the cap: the relative criteria met early and late, and max_iterations reached
+    assert min(its) <= 2 and max(its) == ref.MAX_ITER and any(2 < i < ref.MAX_ITER for i in its), its
+
+
+def test_ldlt_and_increment_against_the_oracle_solver():
+    """ldlt_solve6 + vec6_to_mat4 (libm) == oracle.ref_solver666 bit for bit, on SPD systems and on singular ones
+    (zero rows: the pivoting and the D^+ branch)."""
+    rng = np.random.default_rng(5)
+    for k in range(40):
+        M = rng.normal(size=(6, 6)).astype(F)
+        if k % 4 == 3:
+            M[:, rng.integers(0, 6)] = 0
+            M[rng.integers(0, 6)] = 0
+        A = (M @ M.T).astype(F)
+        A = np.triu(A) + np.triu(A, 1).T
+        if k % 4 == 3:
+            j = int(rng.integers(0, 6))
+            A[j, :] = 0
+            A[:, j] = 0
+        b = (0.05 * rng.normal(size=6)).astype(F)
+        acc = np.zeros(29, F)
+        acc[:21] = A[np.triu_indices(6)]
+        acc[21:27] = b
+        want = oracle.ref_solver666(A, b)
+        got = ref.vec6_to_mat4(ref.ldlt_solve6(acc), "libm")
+        assert ref.same_bits(got, want), k
+
+
+# -- 2. known answers in wave order -------------------------------------------------------------------------------
+
+def test_the_scenes_own_cloud_gives_the_identity(c1, scene):
+    pcd, nrm = scene
+    src = np.where(c1.src_depth_cm > 0, c1.src_depth_cm, 0).astype(np.int32)
+    pcd, nrm = oracle.ref_scene(src, *_cam(c1))
+    cloud = oracle.ref_depth2cloud(src, *_cam(c1))[::7]
+    T, fit, rmse, it, _ = ref.icp(cloud, pcd, nrm, *_cam(c1))
+    assert fit == 1.0 and rmse == 0.0 and it == 1
+    assert np.array_equal(T, np.eye(4, dtype=F))
+
+
+def test_empty_and_out_of_image_clouds_give_the_identity_at_iteration_0(c1, scene):
+    pcd, nrm = scene
+    outside = np.array([[5.0, 0.0, 0.8], [0.0, -5.0, 0.8], [0.1, 0.1, -0.8], [np.nan, 0.0, 1.0], [0.0, 0.0, 0.0],
+                        [1e30, 0.0, 1e-30]], F)
+    for cloud in (np.zeros((0, 3), F), outside):
+        T, fit, rmse, it, _ = ref.icp(cloud, pcd, nrm, *_cam(c1))
+        assert it == 0 and fit == 0.0 and rmse == 0.0 and np.array_equal(T, np.eye(4, dtype=F))
+
+
+def test_max_iterations_0_returns_at_iteration_0_with_the_measures(c1, scene):
+    pcd, nrm = scene
+    cloud = _clouds(c1, c1.poses[[c1.gt_index]], 8)[0]
+    T, fit, rmse, it, moved = ref.icp(cloud, pcd, nrm, *_cam(c1), max_iterations=0)
+    assert it == 0 and fit > 0.5 and rmse > 0.0
+    assert np.array_equal(T, np.eye(4, dtype=F)) and np.array_equal(moved, cloud)
+    _, fit1, rmse1, it1, _ = ref.icp(cloud, pcd, nrm, *_cam(c1), max_iterations=1)
+    assert it1 == 1 and (fit1, rmse1) != (fit, rmse)
+
+
+# -- 3. wave order near the ground truth ------------------------------------------------------------------------------
+
+# Measured on the 32 cases below (16 perturbations x strides 8 and 4), wave order + spec trigonometry against
+# oracle.ref_icp: see MEASURED_* and DESIGN.md section 5.  A one-point association flip is the unit of change, so the
+# test allows three times the measured maximum.
+MEASURED_MAX_DRMSE = 1.55e-4     # at rmse 2.4e-3 .. 3.3e-3
+MEASURED_MAX_DFITNESS = 1.9e-3   # max |d T| was 4.3e-3 and the iteration counts differed on 5 of the 32: not asserted
+
+
+def perturbed_gt_poses(c1, n=16, seed=20):
+    """n seeded perturbations of the C1 ground-truth pose: a rotation of about 1.5 degrees standard deviation about
+    the object's own origin and a translation within +-6 mm."""
+    rng = np.random.default_rng(seed)
+    P = c1.poses[c1.gt_index].astype(np.float64).reshape(4, 4).copy()
+    P[:3] /= 100.0
+    out = []
+    for _ in range(n):
+        w = rng.normal(0.0, np.deg2rad(1.5) / np.sqrt(3.0), 3)
+        th = np.linalg.norm(w)
+        K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+        R = np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * (K @ K)
+        D = np.eye(4)
+        D[:3, :3] = R
+        M = P @ D
+        M[:3, 3] += rng.uniform(-0.006, 0.006, 3)
+        out.append(M)
+    return init_from_eigen_batch(np.stack(out))
+
+
+def wave_against_oracle(c1, scene):
+    """(|d rmse|, |d fitness|, max |d T|, iterations differ, oracle rmse) per case, strides 8 then 4."""
+    pcd, nrm = scene
+    poses = perturbed_gt_poses(c1)
+    rows = []
+    for stride in (8, 4):
+        for cloud in _clouds(c1, poses, stride):
+            T0, f0, r0, it0, _ = oracle.ref_icp(cloud, pcd, nrm, *_cam(c1))
+            T1, f1, r1, it1, _ = ref.icp(cloud, pcd, nrm, *_cam(c1))
+            rows.append((abs(float(r1) - r0), abs(float(f1) - f0), float(np.abs(T1 - T0).max()), it1 != it0, r0))
+    return np.array(rows, np.float64)
+
+
+def test_wave_order_costs_no_quality_near_the_ground_truth(c1, scene):
+    m = wave_against_oracle(c1, scene)
+    assert len(m) == 32
+    print(f"max |d rmse| {m[:, 0].max():.3g}, max |d fitness| {m[:, 1].max():.3g}, max |d T| {m[:, 2].max():.3g}, "
+          f"iterations differ on {int(m[:, 3].sum())} of {len(m)}, oracle rmse {m[:, 4].min():.3g}..{m[:, 4].max():.3g}")
+    assert m[:, 0].max() <= 3 * MEASURED_MAX_DRMSE
+    assert m[:, 1].max() <= 3 * MEASURED_MAX_DFITNESS

@@ -6,6 +6,8 @@ multi-GPU configs).  Prints one JSON line per config.  Not the driver's bench (b
       side of the workload bench.py's cpu_reference_path times on the reference's CPU/OMP path
   c1_planar  C1's scene and grid scaled to 20,000 states: the planar (x, y, yaw) ICP stage, the two-pass 3-DoF search
       and GICP on the same states (not in the default list: --configs c1_planar)
+  c1_p2p  the same 20,000 states: the point-to-plane projective ICP stage beside the planar ICP stage and GICP
+  c3_p2p  C3's batch through evaluate_p2p (point-to-plane ICP + re-score) beside evaluate_icp (GICP + re-score)
   C2  1 mesh, 10k poses, render + score, 640x480
   C3  5 objects, 50k poses, render + GICP + re-render + score, 640x480 (+ argmin vs GT)
   C4  21 objects, 200k poses over 8 GPUs -> 25k poses per GPU, render + score
@@ -154,13 +156,9 @@ def run_c1(steps, warmup, stride=4):
                       "observed_points": int(xyz.shape[0])}), flush=True)
 
 
-def run_c1_planar(nxy=50, stride=4, runs=5, host_poses=16):
-    """c1_planar: C1's table-top scene and grid scaled to nxy x nxy x 8 states (20,000), refined by the planar
-    (x, y, yaw) ICP.  Reports the planar stage alone (PoseCore.icp_planar), the two-pass search (planar ICP, the host
-    pose update and pose rebuild, stage COST with the selection) and, as the yardstick, the only refinement the library
-    had for these states before: evaluate_icp (GICP) at 3-DoF on the same context -- `runs` alternating runs each,
-    medians.  For context also the numpy restatement of the spec (tests/icp2d_reference.py) on host_poses poses, one
-    thread each, in the place of the reference's OpenMP loop."""
+def c1_grid(nxy, stride):
+    """C1's table-top scene with its observation set, and C1's 4 x 4 cells of 4 cm around the ground truth cut into
+    nxy x nxy positions with its 8 yaws: the states of c1_planar and c1_p2p."""
     from perception_amd.core import PoseCore
     from perception_amd.model import compute_proj
     from perception_amd.recognizer import preprocessing_transform
@@ -192,6 +190,21 @@ def run_c1_planar(nxy=50, stride=4, runs=5, host_poses=16):
     poses = torch.from_numpy(pose_in_cam_3dof(sc.camera_pose, pre, model0, states)).to(dev)
     pm = torch.zeros(n, dtype=torch.int32, device=dev)
     tot = torch.full((n,), float(xyz.shape[0]), dtype=torch.float32, device=dev)
+    return dict(core=core, sc=sc, pre=pre, xyz=xyz, states=states, model0=model0, M=M, poses=poses, pm=pm, tot=tot,
+                n=n, W=W, H=H, dev=dev)
+
+
+def run_c1_planar(nxy=50, stride=4, runs=5, host_poses=16):
+    """c1_planar: C1's table-top scene and grid scaled to nxy x nxy x 8 states (20,000), refined by the planar
+    (x, y, yaw) ICP.  Reports the planar stage alone (PoseCore.icp_planar), the two-pass search (planar ICP, the host
+    pose update and pose rebuild, stage COST with the selection) and, as the yardstick, the only refinement the library
+    had for these states before: evaluate_icp (GICP) at 3-DoF on the same context -- `runs` alternating runs each,
+    medians.  For context also the numpy restatement of the spec (tests/icp2d_reference.py) on host_poses poses, one
+    thread each, in the place of the reference's OpenMP loop."""
+    from perception_amd.tabletop import planar_adjusted_states, pose_in_cam_3dof
+    g = c1_grid(nxy, stride)
+    core, sc, pre, xyz, states, model0, M = (g[k] for k in ("core", "sc", "pre", "xyz", "states", "model0", "M"))
+    poses, pm, tot, n, W, H, dev = (g[k] for k in ("poses", "pm", "tot", "n", "W", "H", "dev"))
     keys = torch.full((1,), PCORE_KEY_NONE, dtype=torch.int64, device=dev)
     out_p = None
 
@@ -253,6 +266,89 @@ def run_c1_planar(nxy=50, stride=4, runs=5, host_poses=16):
     print(json.dumps(res), flush=True)
 
 
+def _once(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def run_c1_p2p(nxy=50, stride=4, runs=5):
+    """c1_p2p: the point-to-plane projective ICP stage (PoseCore.icp_point2plane) on c1_planar's 20,000 states, beside
+    the planar ICP stage and GICP (the evaluate_icp call and its GICP stage alone) on the same context -- `runs`
+    alternating runs each after one warm-up, medians."""
+    g = c1_grid(nxy, stride)
+    core, poses, pm, tot, M, n = (g[k] for k in ("core", "poses", "pm", "tot", "M", "n"))
+    out = {"p2p": None, "planar": None}
+
+    def p2p():
+        out["p2p"] = core.icp_point2plane(poses, pm, None, cost_type=0, stride=stride, out=out["p2p"])
+
+    def planar():
+        out["planar"] = core.icp_planar(poses, pm, M, stride=stride, out=out["planar"])
+
+    def gicp():
+        core.evaluate_icp(poses, pm, None, tot, cost_type=0, stride=stride, sensor_resolution=0.0075)
+
+    for fn in (p2p, planar, gicp):  # warm-up: scratch, the scene, grids, target covariances
+        _once(fn)
+    t = {"p2p": [], "planar": [], "gicp": []}
+    gicp_stage = []
+    for _ in range(runs):  # alternating
+        t["p2p"].append(_once(p2p))
+        t["planar"].append(_once(planar))
+        t["gicp"].append(_once(gicp))
+        gicp_stage.append(float(core.stats()["icp_runtime"]))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    _, fit, rmse, iters = (x.cpu().numpy() for x in out["p2p"])
+    print(json.dumps({"config": "c1_p2p", "poses": n, "width": g["W"], "height": g["H"], "stride": stride, "runs": runs,
+                      "p2p_s": med["p2p"], "p2p_poses_per_s": n / med["p2p"],
+                      "planar_s": med["planar"], "planar_poses_per_s": n / med["planar"],
+                      "gicp_call_s": med["gicp"], "gicp_call_poses_per_s": n / med["gicp"],
+                      "gicp_stage_s": float(np.median(gicp_stage)),
+                      "p2p_s_all": t["p2p"], "planar_s_all": t["planar"], "gicp_call_s_all": t["gicp"],
+                      "iters_mean": float(iters.mean()), "iters_at_cap": int((iters >= 30).sum()),
+                      "fitness_mean": float(fit.mean()), "rmse_mean": float(rmse.mean())}), flush=True)
+
+
+def run_c3_p2p(per_model=10000, runs=5):
+    """c3_p2p: C3's batch (5 objects, 50k 6-DoF poses) through evaluate_p2p (point-to-plane ICP + re-score) and through
+    evaluate_icp (GICP + re-score) on the same context -- `runs` alternating runs each after one warm-up, medians; the
+    point-to-plane stage alone too."""
+    w = workloads.build(names=C3_NAMES, poses_per_model=per_model, cam=syn.CAM_640)
+    n = int(w.poses.shape[0])
+    res = {}
+
+    def p2p():
+        res["p2p"] = w.core.evaluate_p2p(w.poses, w.pose_model, w.pose_label, w.pose_obs_total, stride=w.stride)
+
+    def p2p_stage():
+        w.core.icp_point2plane(w.poses, w.pose_model, w.pose_label, stride=w.stride)
+
+    def gicp():
+        res["gicp"] = w.core.evaluate_icp(w.poses, w.pose_model, w.pose_label, w.pose_obs_total, stride=w.stride)
+
+    for fn in (p2p, p2p_stage, gicp):
+        _once(fn)
+    t = {"p2p": [], "p2p_stage": [], "gicp": []}
+    gicp_stage = []
+    for _ in range(runs):  # alternating
+        t["p2p"].append(_once(p2p))
+        t["p2p_stage"].append(_once(p2p_stage))
+        t["gicp"].append(_once(gicp))
+        gicp_stage.append(float(w.core.stats()["icp_runtime"]))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    iters = res["p2p"][1].cpu().numpy()
+    print(json.dumps({"config": "c3_p2p", "poses": n, "models": w.num_models, "stride": w.stride, "runs": runs,
+                      "evaluate_p2p_s": med["p2p"], "evaluate_p2p_poses_per_s": n / med["p2p"],
+                      "p2p_stage_s": med["p2p_stage"], "evaluate_icp_s": med["gicp"],
+                      "evaluate_icp_poses_per_s": n / med["gicp"], "gicp_stage_s": float(np.median(gicp_stage)),
+                      "evaluate_p2p_s_all": t["p2p"], "p2p_stage_s_all": t["p2p_stage"], "evaluate_icp_s_all": t["gicp"],
+                      "p2p_iters_mean": float(iters.mean()), "p2p_iters_at_cap": int((iters >= 30).sum()),
+                      "gicp_iters_mean": float(res["gicp"][1].float().mean().item())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4,C5")
@@ -266,6 +362,10 @@ def main():
         run_c1(max(a.steps, 10), max(a.warmup, 2))
     if "c1_planar" in sel:
         run_c1_planar(nxy=max(2, int(round(50 * sc ** 0.5))))
+    if "c1_p2p" in sel:
+        run_c1_p2p(nxy=max(2, int(round(50 * sc ** 0.5))))
+    if "c3_p2p" in sel:
+        run_c3_p2p(per_model=max(1, int(10000 * sc)))
     if "C2" in sel:
         run("C2", ["003_cracker_box"], int(10000 * sc), syn.CAM_640, False, a.steps, a.warmup)
     if "C3" in sel:
