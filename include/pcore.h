@@ -260,6 +260,14 @@ int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_
                            float fx, float fy, float cx, float cy, const pcore_p2p_icp_params* icp, float* d_out_T,
                            float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream);
 
+/* Test hook (no reference counterpart): stage CLOUD of every pose into caller-made slots, as the ICP entry points
+ * render their source clouds -- pose i's points (x, y, z, 0) in the reference's compaction order (row-major stride
+ * samples, compute_point_clouds.cuh:290-346) at d_out_xyzw + 4 i ws hs, their number in d_out_count[i]; ws = W / stride,
+ * hs = ceil(H / stride).  params: stride, depth_factor and occlusion_threshold are used; d_pose_label as pcore_evaluate. */
+int pcore_debug_render_clouds(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_model,
+                              const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* params,
+                              float* d_out_xyzw, int32_t* d_out_count, pcore_stream stream);
+
 /* Stage "RENDER" / "DEBUG" images (renderer.cu:1594-1615): full-resolution int32 z-buffers (cm) with source
  * occlusion and INT_MAX -> 0 (image_render, image_renderer.cuh:336-496).  d_out_depth: N x H x W.
  * d_out_color (nullable): the reference's result_color -- three planes red, green, blue of N x H x W uint8 each,

@@ -366,6 +366,24 @@ class PoseCore:
                                    color_distance_threshold=color_distance_threshold, stream=stream)
         return adj, iters, rc, oc, df, fitness, rmse
 
+    def render_clouds(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor] = None,
+                      stride: int = 8, depth_factor: float = 100.0, occlusion_threshold: float = 1.0, stream=None
+                      ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """pcore_debug_render_clouds (test hook): stage CLOUD of every pose as the ICP entry points render their source
+        clouds.  Returns (xyzw (N, ws * hs, 4) float32, count (N,) int32): pose i's points are xyzw[i, :count[i]]."""
+        n = int(poses.shape[0])
+        w, h = self.width, self.height
+        nsamp = (w // stride) * ((h + stride - 1) // stride)
+        xyzw = torch.zeros((n, nsamp, 4), dtype=torch.float32, device=poses.device)
+        cnt = torch.zeros(n, dtype=torch.int32, device=poses.device)
+        p = EvalParams(_native.COST_DEPTH_6DOF, 0, int(stride), float(depth_factor), 0.0, float(occlusion_threshold),
+                       0.0)
+        self._check(self.lib.pcore_debug_render_clouds(
+            self._h, _ptr(poses, torch.float32, "poses"), _ptr(pose_model, torch.int32, "pose_model"),
+            _ptr(pose_label, torch.int32, "pose_label"), n, ctypes.byref(p), _ptr(xyzw, torch.float32, "xyzw"),
+            _ptr(cnt, torch.int32, "count"), _stream(stream)))
+        return xyzw, cnt
+
     def render(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
                occlusion_threshold: float = 1.0, out: Optional[torch.Tensor] = None, color: bool = False,
                out_color: Optional[torch.Tensor] = None, stream=None):

@@ -1471,6 +1471,47 @@ int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_
     return launch_p2p_icp(g, num_segs, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
 }
 
+// Test hook: stage CLOUD into caller-made slots (render_cloud_kernel as pcore_evaluate_icp, pcore_icp_planar and
+// pcore_icp_point2plane launch it, without the covariances).  Every check comes before the launch.
+int pcore_debug_render_clouds(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model,
+                              const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* p,
+                              float* d_out_xyzw, int32_t* d_out_count, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (!p) return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: null parameters");
+    if (!c->have_mesh || !c->have_cam || !c->have_obs)
+        return fail(c, PCORE_E_STATE, "debug_render_clouds: meshes, camera and observation must be set first");
+    if (num_poses < 0 || (num_poses > 0 && (!d_poses || !d_pose_model || !d_out_xyzw || !d_out_count)))
+        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: null pose / output pointer");
+    if (d_pose_label && !c->obs_has_mask)
+        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: pose labels need a source mask");
+    const int W = c->cam.width, H = c->cam.height;
+    if (p->stride <= 0 || W % p->stride != 0)
+        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: width must be a multiple of stride");
+    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
+    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: sampled image too large");
+    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
+        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: sampled z-buffer does not fit in LDS");
+    if (num_poses == 0) return PCORE_OK;
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    int rc = ensure_sampled(c, p->stride, s);
+    if (rc != PCORE_OK) return rc;
+    FusedArgs a{};
+    fill_fused_args(c, p, a);
+    a.poses = d_poses;
+    a.pose_model = d_pose_model;
+    a.pose_label = d_pose_label;
+    a.num_poses = num_poses;
+    a.cloud_out = (float4*)d_out_xyzw;
+    a.cloud_count = d_out_count;
+    a.cloud_cap = ws * hs;
+    a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
+    if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
+    if (a.tcap <= 0) a.tcap = a.ws * a.hs;
+    HIPC(c, launch_render_cloud(a, s));
+    return PCORE_OK;
+}
+
 int pcore_render(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
                  int32_t num_poses, float occlusion_threshold, int32_t* d_out_depth, uint8_t* d_out_color,
                  pcore_stream stream) {

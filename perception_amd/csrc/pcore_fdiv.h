@@ -76,6 +76,39 @@ __device__ __forceinline__ bool absbits_range_ok(uint32_t umin, uint32_t umax) {
     return umin >= (87u << 23) && umax < (168u << 23);
 }
 
+// The fragment test's barycentrics without the reference's three halves (fragment<true>, pcore_kernels.hip).  The
+// reference computes area = 0.5 Y, beta = (0.5 X) * (1 / area) with Y and X the rounded cross products of coordinate
+// differences.  Scaling a float by 0.5 or 2 is exact unless the result is denormal or overflows, and commutes with a
+// correctly rounded division under the same condition, so
+//     fl(1 / fl(0.5 Y)) = 2 fl(1 / Y)     and     fl(fl(0.5 X) * (2 fl(1 / Y))) = fl(X * fl(1 / Y))
+// (the last pair rounds the same real product, whatever its magnitude) whenever
+//     Y = 0, or 2^-125 <= |Y| < 2^126 (0.5 Y normal; 1 / Y normal and 2 / Y finite),   and   X = 0 or |X| >= 2^-125.
+// Zero, infinite and NaN values pass through both forms alike (0.5 and 2 keep them): a zero area gives the same
+// signed infinity, and then the same infinite or NaN barycentrics, which count as inside.
+// The bound holds for every fastdiv pose (pose_window: every vertex has 1 <= z and |px|, |py| < 2^40 before the
+// division) of a camera with 1 <= W, H <= 2^16 (pcore_set_camera accepts 16384 at most):
+//   - a screen coordinate is fl(t + h) with h = W/2 or H/2 in [2^-1, 2^15] and t = fl(q h), |q| <= 2^40 (1 + 2^-23).
+//     Where |t| >= h/2, t and h are multiples of ulp(h/2) >= 2^-25, and so are their sum and its rounding; where
+//     |t| < h/2 the sum lies in (h/2, 3h/2) and its rounding is a multiple of ulp(h/2).  So every screen coordinate,
+//     and every sample centre (an integer), is a multiple of g = 2^-25, of magnitude below 2^56;
+//   - a coordinate difference is then a multiple of g below 2^57 (rounding keeps multiples of g), a product of two a
+//     multiple of g^2 = 2^-50 below 2^114, and X, Y -- differences of two products -- are 0 or in [2^-50, 2^115).
+// NOHALF = false is the reference's form (image_renderer.cuh:44-57, 112-121).
+template <bool NOHALF>
+__device__ __forceinline__ void frag_barycentrics(float A0, float A1, float B0, float B1, float C0, float C1, float P0,
+                                                  float P1, float& beta, float& gamma) {
+    if constexpr (NOHALF) {
+        const float base_inv = 1.0f / ((C0 - A0) * (B1 - A1) - (B0 - A0) * (C1 - A1));
+        beta = ((C0 - A0) * (P1 - A1) - (P0 - A0) * (C1 - A1)) * base_inv;
+        gamma = ((P0 - A0) * (B1 - A1) - (B0 - A0) * (P1 - A1)) * base_inv;
+    } else {
+        const float area = 0.5f * ((C0 - A0) * (B1 - A1) - (B0 - A0) * (C1 - A1));
+        const float base_inv = 1.0f / area;
+        beta = 0.5f * ((C0 - A0) * (P1 - A1) - (P0 - A0) * (C1 - A1)) * base_inv;
+        gamma = 0.5f * ((P0 - A0) * (B1 - A1) - (B0 - A0) * (P1 - A1)) * base_inv;
+    }
+}
+
 // The fragment depth of the reference (image_renderer.cuh:123-129) from its barycentrics and vertex depths, with IEEE
 // divisions in the reference's order: int32_t((alpha + beta + gamma) / (alpha/z0 + beta/z1 + gamma/z2) + 0.5f).
 __device__ __forceinline__ int32_t frag_depth_ieee(float alpha, float beta, float gamma, float z0, float z1, float z2) {

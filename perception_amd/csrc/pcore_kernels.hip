@@ -36,6 +36,15 @@
 #ifndef PCORE_STEP_UNROLL
 #define PCORE_STEP_UNROLL 1
 #endif
+// A/B switches of the instruction cuts of DESIGN.md section 4 (each 1 = on; every setting computes the same bits):
+// the fastdiv depth pass's fragment test without its three halves, and the projection's sparse flag made once per
+// workgroup with the pose window
+#ifndef PCORE_FRAG_NOHALF
+#define PCORE_FRAG_NOHALF 1
+#endif
+#ifndef PCORE_WIN_SPARSE
+#define PCORE_WIN_SPARSE 1
+#endif
 
 namespace pcore {
 
@@ -124,12 +133,13 @@ __device__ __forceinline__ bool loop_bounds(float bmin, float bmax, int& lo, int
 // Returns whether the pixel is inside (NaN barycentrics count as inside, as in the reference) and sets the depth
 // for inside pixels; every lane runs the same instructions (no branch on the inside test), so a batch of
 // fragment tests is one straight-line block plus the depth's rare IEEE fallback.
+// NOHALF: the barycentrics without the reference's three multiplications by 0.5, bit-identical under the bound of a
+// fastdiv pose (pcore_fdiv.h); only the depth pass of a fastdiv pose asks for it.
+template <bool NOHALF = false>
 __device__ __forceinline__ bool fragment(float A0, float A1, float B0, float B1, float C0, float C1, float z0,
                                          float z1, float z2, float P0, float P1, int32_t& depth, bool z_ok = false) {
-    const float area = 0.5f * ((C0 - A0) * (B1 - A1) - (B0 - A0) * (C1 - A1));
-    const float base_inv = 1.0f / area;
-    const float beta = 0.5f * ((C0 - A0) * (P1 - A1) - (P0 - A0) * (C1 - A1)) * base_inv;
-    const float gamma = 0.5f * ((P0 - A0) * (B1 - A1) - (B0 - A0) * (P1 - A1)) * base_inv;
+    float beta, gamma;
+    frag_barycentrics<NOHALF && PCORE_FRAG_NOHALF>(A0, A1, B0, B1, C0, C1, P0, P1, beta, gamma);
     const float alpha = 1.0f - beta - gamma;
     // !(alpha < -0 || beta < -0 || gamma < -0 || alpha > 1 || beta > 1 || gamma > 1) as one v_min3 / v_max3 each:
     // the three are arithmetic results (quiet NaNs at most), on which v_min3 / v_max3 follow IEEE minNum / maxNum
@@ -210,7 +220,7 @@ struct FusedSmem {
     uint2* ring;    // kWaves * kRecStride queued triangle records (phase 1); int32 point queues in phase 2
     uint32_t* ring_id;  // kWaves * kRecStride original triangle ids (colour id pass only)
     uint32_t* bitmap;
-    int32_t* counters;  // [0] bad, [1] explained, [2] points; [4..8] the pose window (x0, y0, nx, ny, fastdiv)
+    int32_t* counters;  // [0] bad, [1] explained, [2] points; [4..9] the pose window (x0, y0, nx, ny, fastdiv, sparse)
 };
 constexpr int kRingSlots = kVRing * kWave;
 static_assert(kRingSlots <= (1 << kRingSlotBits), "vertex ring slots must fit the 9-bit triangle indices");
@@ -227,15 +237,19 @@ struct SampleWin {
     // every vertex of the pose has 1 <= z < 2^41 and |x|, |y| < 2^41 after the projection (pose_window's bounds),
     // so the vertex pass needs no per-vertex range check of its unscaled division (see the vertex pass)
     int fastdiv;
+    // the vertex stage may skip the projection's zero entries (raster_phase): a.proj_sparse, every model vertex
+    // finite and the camera rows' bounds over the model's box far from FLT_MAX
+    int sparse;
 };
 
-template <bool IDPASS = false>
+template <bool IDPASS = false, bool NOHALF = false>
 __device__ __forceinline__ void raster_sample(const TriRec& r, int kx, int ky, int s, int H, const SampleWin& w,
                                               int32_t* zbuf, int32_t* cid = nullptr, uint32_t id = 0) {
     const float P0 = (float)(kx * s);
     const float P1 = (float)(H - 1 - ky * s);
     int32_t d;
-    const bool in = fragment(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d, w.fastdiv != 0);
+    const bool in = fragment<NOHALF>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d,
+                                     w.fastdiv != 0);
     const int k = (int)__umul24((uint32_t)(ky - w.y0), (uint32_t)w.nx) + (kx - w.x0);  // inside the window
     if constexpr (IDPASS) {
         if (in && d == zbuf[k]) atomicMin(&cid[k], (int32_t)id);
@@ -255,7 +269,7 @@ size_t fused_lds_bytes(int tile_samples, int bitmap_words, bool colour) {
     b += al((size_t)kWaves * kRecStride * 8);
     if (colour) b += al((size_t)kWaves * kRecStride * 4);
     b += al((size_t)bitmap_words * 4);
-    b += 48;  // counters: [0] bad, [1] explained, [2] points; [4..8] the pose window (fused_cost_kernel)
+    b += 48;  // counters: [0] bad, [1] explained, [2] points; [4..9] the pose window (fused_cost_kernel)
     return b;
 }
 
@@ -387,6 +401,8 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                                              int32_t* cid, FProf& fp) {
     SampleWin sw = sw_in;
     if constexpr (FD >= 0) sw.fastdiv = FD;
+    // the fragment test without its halves: the depth pass of a fastdiv pose only (pcore_fdiv.h)
+    constexpr bool kNoHalf = FD == 1 && !IDPASS;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar loads of stream headers
     const int lane = tid & 63;
@@ -403,6 +419,10 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
     // does not see (both give W/2 exactly) -- as long as the skipped products 0 * y are zeros, i.e. the camera
     // point is finite.  It is when every model vertex is finite (model_box flag) and the bound of |row . v|
     // over the model's box (B below, as in pose_window) stays far from FLT_MAX; NaN entries fail the test.
+    // The test is pose_window's (SampleWin::sparse), made once per workgroup with the window.
+#if PCORE_WIN_SPARSE
+    const bool proj_sparse = sw.sparse != 0;
+#else
     bool proj_sparse = false;
     if (a.proj_sparse && model >= 0 && model < a.num_models) {
         const float4 lo = a.model_box[2 * model], hi = a.model_box[2 * model + 1];
@@ -412,6 +432,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
         const float By = fabsf(m10) * ax + fabsf(m11) * ay + fabsf(m12) * az + fabsf(m13);
         proj_sparse = lo.w != 0.0f && Bx < 1.0e30f && By < 1.0e30f;
     }
+#endif
     __syncthreads();
 
     // ---------------- phase 1: raster of the sampled pixels ----------------
@@ -467,7 +488,8 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
 #ifdef PCORE_FLUSH_STATS
                     atomicAdd(&pcore_flush_stats[2], 1ull);
 #endif
-                    raster_sample<IDPASS>(r, (int)(rec.y & 0xffffu), (int)(rec.y >> 16), s, H, sw, sm.zbuf, cid, id);
+                    raster_sample<IDPASS, kNoHalf>(r, (int)(rec.y & 0xffffu), (int)(rec.y >> 16), s, H, sw, sm.zbuf,
+                                                   cid, id);
                 }
             }
         }
@@ -674,7 +696,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                         for (int q = lane; q < bnk; q += kWave) {
                             int iy = (int)(((float)q + 0.5f) * inv_nx), ix = q - iy * bnx;
                             if (ix < 0) { iy--; ix += bnx; } else if (ix >= bnx) { iy++; ix -= bnx; }
-                            raster_sample<IDPASS>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid);
+                            raster_sample<IDPASS, kNoHalf>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid);
                         }
                     } while (big);
                 }
@@ -743,8 +765,15 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
 // not finite or comes within 5 % of its depth magnitude of the camera plane.  Wave-uniform; every wave of
 // the workgroup computes the same window.
 __device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)[12], int s) {
-    const SampleWin whole = {0, 0, a.ws, a.hs, 0};
     const float4 lo = a.model_box[2 * model], hi = a.model_box[2 * model + 1];
+    // magnitude of the terms of each camera row over the box (bounds the rounding of any vertex's row)
+    const float ax = fmaxf(fabsf(lo.x), fabsf(hi.x)), ay = fmaxf(fabsf(lo.y), fabsf(hi.y));
+    const float az = fmaxf(fabsf(lo.z), fabsf(hi.z));
+    const float Bx = fabsf(m[0]) * ax + fabsf(m[1]) * ay + fabsf(m[2]) * az + fabsf(m[3]);
+    const float By = fabsf(m[4]) * ax + fabsf(m[5]) * ay + fabsf(m[6]) * az + fabsf(m[7]);
+    const float Bz = fabsf(m[8]) * ax + fabsf(m[9]) * ay + fabsf(m[10]) * az + fabsf(m[11]);
+    const int sparse = (a.proj_sparse && lo.w != 0.0f && Bx < 1.0e30f && By < 1.0e30f) ? 1 : 0;  // NaN bounds fail
+    const SampleWin whole = {0, 0, a.ws, a.hs, 0, sparse};
     const int c = lane_id() & 7;
     const float x = (c & 1) ? hi.x : lo.x, y = (c & 2) ? hi.y : lo.y, z = (c & 4) ? hi.z : lo.z;
     const float Wf = (float)a.width, Hf = (float)a.height;
@@ -768,12 +797,6 @@ __device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)
     auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
     lzmin = uni(lzmin); sx0 = uni(sx0); sx1 = uni(sx1); sy0 = uni(sy0); sy1 = uni(sy1);
     if ((__ballot(bad) & 0xffull) || lo.w == 0.0f) return whole;
-    // magnitude of the terms of each camera row over the box (bounds the rounding of any vertex's row)
-    const float ax = fmaxf(fabsf(lo.x), fabsf(hi.x)), ay = fmaxf(fabsf(lo.y), fabsf(hi.y));
-    const float az = fmaxf(fabsf(lo.z), fabsf(hi.z));
-    const float Bx = fabsf(m[0]) * ax + fabsf(m[1]) * ay + fabsf(m[2]) * az + fabsf(m[3]);
-    const float By = fabsf(m[4]) * ax + fabsf(m[5]) * ay + fabsf(m[6]) * az + fabsf(m[7]);
-    const float Bz = fabsf(m[8]) * ax + fabsf(m[9]) * ay + fabsf(m[10]) * az + fabsf(m[11]);
     if (!(lzmin > 0.05f * Bz)) return whole;
     // |error of sx| <= (W/2) (Pbx / lzmin) eps (8 + 4 Bz / lzmin) + 4 eps (|sx| + W), Bz / lzmin <= 20
     const float eps = 5.9604645e-8f;
@@ -789,8 +812,9 @@ __device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)
     const int Y0 = max(0, (int)floorf((Hf - 1.0f - yhi) / sf)), Y1 = min(a.hs - 1, (int)floorf((Hf - ylo) / sf));
     // Every vertex's computed z is at least the corners' minimum less the rounding of two dot products
     // (<= 6 eps Bz); the margin 1e-5 Bz covers that.  |x|, |y| after the projection are below Pbx, Pby.
+    // (The fragment test of a fastdiv pose relies on these bounds too: pcore_fdiv.h, frag_barycentrics.)
     const bool fastdiv = lzmin - 1.0e-5f * Bz >= 1.0f && Bz < 0x1p40f && Pbx < 0x1p40f && Pby < 0x1p40f;
-    return SampleWin{X0, Y0, max(0, X1 - X0 + 1), max(0, Y1 - Y0 + 1), fastdiv ? 1 : 0};
+    return SampleWin{X0, Y0, max(0, X1 - X0 + 1), max(0, Y1 - Y0 + 1), fastdiv ? 1 : 0, sparse};
 }
 
 // One pose of stage COST on the workgroup's LDS tile (sw.nx * sw.ny <= tile capacity).
@@ -994,7 +1018,8 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
         for (int r0 = 0; r0 < pw.ny; r0 += ch)
             for (int c0 = 0; c0 < pw.nx; c0 += cw) {
                 if (r0 > 0 || c0 > 0) __syncthreads();  // the previous chunk's points are processed
-                chunk(SampleWin{pw.x0 + c0, pw.y0 + r0, min(cw, pw.nx - c0), min(ch, pw.ny - r0), pw.fastdiv});
+                chunk(SampleWin{pw.x0 + c0, pw.y0 + r0, min(cw, pw.nx - c0), min(ch, pw.ny - r0), pw.fastdiv,
+                                pw.sparse});
             }
     }
     // per-wave totals
@@ -1083,7 +1108,7 @@ fused_cost_kernel(FusedArgs a) {
     // the pose window, by wave 0 only (every wave would compute the same one), shared through LDS
     if (threadIdx.x < kWave) {
         const int model = a.pose_model[pose];
-        SampleWin w = {0, 0, 0, 0, 0};  // invalid model: nothing is rendered
+        SampleWin w = {0, 0, 0, 0, 0, 0};  // invalid model: nothing is rendered
         if (model >= 0 && model < a.num_models) {
             float m[12];
             load_pose_rows(a.poses, pose, m);
@@ -1095,12 +1120,14 @@ fused_cost_kernel(FusedArgs a) {
             sm.counters[6] = w.nx;
             sm.counters[7] = w.ny;
             sm.counters[8] = w.fastdiv;
+            sm.counters[9] = w.sparse;
         }
     }
     __syncthreads();
     const SampleWin sw = {__builtin_amdgcn_readfirstlane(sm.counters[4]), __builtin_amdgcn_readfirstlane(sm.counters[5]),
                           __builtin_amdgcn_readfirstlane(sm.counters[6]), __builtin_amdgcn_readfirstlane(sm.counters[7]),
-                          __builtin_amdgcn_readfirstlane(sm.counters[8])};
+                          __builtin_amdgcn_readfirstlane(sm.counters[8]),
+                          __builtin_amdgcn_readfirstlane(sm.counters[9])};
     const int tn = sw.nx * sw.ny;
     // Tile feedback, double-buffered by launch parity: every workgroup counts its window into this launch's
     // histogram (and, when chunked, the chunked-pose count) with atomics whose result it does not wait for;
@@ -1183,7 +1210,7 @@ __global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
     const int cap = a.tcap > 0 && a.tcap < nsamp ? a.tcap : nsamp;  // the LDS tile (samples)
     const FusedSmem sm = carve_smem(smem_raw, cap, 0);
     const int model = a.pose_model[pose];
-    SampleWin sw = {0, 0, 0, 0, 0};
+    SampleWin sw = {0, 0, 0, 0, 0, 0};
     if (model >= 0 && model < a.num_models) {
         float m[12];
         load_pose_rows(a.poses, pose, m);
@@ -1245,7 +1272,8 @@ __global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
         const int cw = min(sw.nx, cap), ch = max(1, cap / max(cw, 1));
         for (int r0 = 0; r0 < sw.ny; r0 += ch)
             for (int c0 = 0; c0 < sw.nx; c0 += cw)
-                chunk(SampleWin{sw.x0 + c0, sw.y0 + r0, min(cw, sw.nx - c0), min(ch, sw.ny - r0), sw.fastdiv});
+                chunk(SampleWin{sw.x0 + c0, sw.y0 + r0, min(cw, sw.nx - c0), min(ch, sw.ny - r0), sw.fastdiv,
+                                sw.sparse});
     }
     if (tid == 0) a.cloud_count[pose] = carry_s < a.cloud_cap ? carry_s : a.cloud_cap;
     // the source covariances of the cloud this workgroup has just written: pcore_cov.h's rounds of

@@ -3,14 +3,15 @@
 // experiments on the CPU.
 //
 // Input: one model's triangles as unique-vertex ids (tv, 3 per triangle) and the vertex positions.  The
-// triangles are put in a locality order (greedy adjacency growth, or a sweep of normal-binned surface patches when
-// that needs fewer vertex passes), cut into `num_streams` contiguous streams
+// triangles are put in a locality order (greedy adjacency growth, a sweep of normal-binned surface patches or bands
+// around an axis, whichever the ring simulation finds cheapest: build_model), cut into `num_streams` contiguous streams
 // of near-equal length, and every stream is turned into steps by simulating the kernel's vertex ring:
 //   - a vertex pass loads the vertices the next triangles miss -- those not loaded by the previous pass --
 //     in order of first use, up to 64;
 //   - the following batches take triangles in order while all three vertices were loaded by the last two
 //     passes (kRefPasses), 64 per step; a partial batch left when the next triangle needs a new pass is
-//     carried past that pass (reloading its vertices the pass would age out), so batches stay full.
+//     carried past that pass (reloading its vertices the pass would age out), so batches stay full.  With a
+//     look-ahead (build_model's candidates) a batch also takes such triangles from behind one that has to wait.
 // Layout (no per-step header, so the kernel never waits on a separate uniform load): every triangle slot of a
 // step carries the step's "vertex pass first" flag in bit 30, padding slots have bit 31 set, and a vertex
 // slot's w is 1 for a vertex, 0 for padding.
@@ -147,6 +148,71 @@ inline std::vector<int> sweep_order(const std::vector<int>& tv, const std::vecto
     return order;
 }
 
+// Band order: the surface as closed bands around a coordinate axis, each swept once around the axis, between two
+// caps.
+// A triangle whose normal is within 45 degrees of the axis belongs to the cap on its side; the others are binned
+// into `bands` slices of equal height along the axis, and a band is ordered by the azimuth of its triangles' centroids
+// about the axis through the centre of the model's box (stable for equal keys).  A band's "row" -- the triangles of
+// one azimuth -- spans the band's height only, so with enough bands two consecutive rows fit the two-pass window
+// whatever the girth of the model, and a band crosses the edges between the side faces of a box without loading
+// them again.  The caps are swept in rows across their shorter extent.  build_model tries a few band counts per axis
+// and keeps an order only where the ring simulation says it is cheaper.
+inline std::vector<int> band_order(const std::vector<int>& tv, const std::vector<float>& vxyz, int axis, int bands) {
+    const int T = (int)tv.size() / 3, NV = (int)vxyz.size() / 3;
+    const int u = (axis + 1) % 3, v = (axis + 2) % 3;
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool any = false;
+    for (int i = 0; i < NV; i++) {
+        const float* p = &vxyz[3 * i];
+        if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = any ? std::min(lo[k], (double)p[k]) : p[k];
+            hi[k] = any ? std::max(hi[k], (double)p[k]) : p[k];
+        }
+        any = true;
+    }
+    const double cu = 0.5 * (lo[u] + hi[u]), cv = 0.5 * (lo[v] + hi[v]);
+    const double h0 = lo[axis], hspan = hi[axis] - lo[axis];
+    const bool caps_along_u = hi[u] - lo[u] >= hi[v] - lo[v];  // cap rows across the shorter extent
+    struct Key {
+        int bin;
+        double k;
+        int t;
+    };
+    std::vector<Key> key(T);
+    for (int t = 0; t < T; t++) {
+        const float* a = &vxyz[3 * tv[3 * t]];
+        const float* b = &vxyz[3 * tv[3 * t + 1]];
+        const float* c = &vxyz[3 * tv[3 * t + 2]];
+        const double e1[3] = {(double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2]};
+        const double e2[3] = {(double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2]};
+        const double n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2],
+                             e1[0] * e2[1] - e1[1] * e2[0]};
+        const double ctr[3] = {((double)a[0] + b[0] + c[0]) / 3.0, ((double)a[1] + b[1] + c[1]) / 3.0,
+                               ((double)a[2] + b[2] + c[2]) / 3.0};
+        const double nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+        Key& q = key[t];
+        q.t = t;
+        if (!(std::isfinite(nn) && std::isfinite(ctr[0]) && std::isfinite(ctr[1]) && std::isfinite(ctr[2]))) {
+            q.bin = bands + 2;  // not finite: last, in index order
+            q.k = 0.0;
+        } else if (2.0 * n[axis] * n[axis] > nn) {  // a cap
+            q.bin = n[axis] < 0.0 ? 0 : bands + 1;
+            q.k = caps_along_u ? ctr[u] : ctr[v];
+        } else {
+            int bi = hspan > 0.0 ? (int)((ctr[axis] - h0) / hspan * bands) : 0;
+            q.bin = 1 + std::max(0, std::min(bands - 1, bi));
+            q.k = std::atan2(ctr[v] - cv, ctr[u] - cu);
+        }
+    }
+    std::stable_sort(key.begin(), key.end(),
+                     [](const Key& p, const Key& q) { return p.bin != q.bin ? p.bin < q.bin : p.k < q.k; });
+    std::vector<int> order(T);
+    for (int t = 0; t < T; t++) order[t] = key[t].t;
+    return order;
+}
+
+constexpr int kAhead = 192;                     // build_model's candidates: triangles a batch may look past
 constexpr int kNever = -(1 << 20);              // "latest pass" of a vertex no pass of the stream has loaded
 constexpr uint32_t kStepVertexPass = 1u << 30;  // every triangle slot of a step that begins with a vertex pass
 constexpr uint32_t kSlotPadding = 1u << 31;     // a triangle slot past the batch
@@ -157,7 +223,8 @@ constexpr uint32_t kSlotPadding = 1u << 31;     // a triangle slot past the batc
 // visible (fragment-producing) triangles and meet at the end-of-raster barrier at similar times.  A chunk
 // boundary only costs the reuse of one vertex pass.
 inline void build_model_order(const std::vector<int>& tv, const std::vector<float>& vxyz, const std::vector<int>& order0,
-                              int tri_base, int num_streams, int vring, int ref_passes, Built& out, int chunks) {
+                              int tri_base, int num_streams, int vring, int ref_passes, Built& out, int chunks,
+                              int ahead = 0) {
     const int T = (int)tv.size() / 3;
     if (T == 0) return;
     const int num_verts = (int)vxyz.size() / 3;
@@ -175,7 +242,8 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
     }
     std::vector<int> latest(num_verts, kNever), slot(num_verts, 0);
     std::vector<char> in_new(num_verts, 0);
-    std::vector<int> newv, batch;
+    std::vector<int> newv, batch, cand;
+    std::vector<char> taken(ahead > 0 ? T : 0, 0);  // by position in `order` (ahead > 0: triangles leave out of turn)
     for (int sidx = 0; sidx < S; sidx++) {
         const int b0 = sidx == 0 ? 0 : stream_end[sidx - 1], b1 = stream_end[sidx];
         I4 sd;
@@ -210,9 +278,39 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
         };
         while (true) {
             // batches: triangles whose vertices were all loaded by the last ref_passes passes, 64 per step
-            while (i < b1 && usable_after(order[i], P)) {
-                batch.push_back(order[i++]);
-                if ((int)batch.size() == 64) emit();
+            if (ahead <= 0) {
+                while (i < b1 && usable_after(order[i], P)) {
+                    batch.push_back(order[i++]);
+                    if ((int)batch.size() == 64) emit();
+                }
+            } else {
+                // ahead > 0: every such triangle among the next ones, past up to `ahead` that have to wait for a
+                // pass (the result does not depend on the triangle order).  A triangle leaves while its vertices are
+                // resident instead of having them loaded again when its turn comes.  Those that name a vertex of the
+                // older pass go first, with the carried batch, so the partial batch left for the next pass to carry
+                // holds triangles of the newest pass as far as possible and the carry reloads little or nothing.
+                cand.assign(batch.begin(), batch.end());
+                batch.clear();
+                int waiting = 0;
+                for (int j = i; j < b1 && waiting <= ahead; j++) {
+                    if (taken[j]) continue;
+                    if (usable_after(order[j], P)) {
+                        taken[j] = 1;
+                        cand.push_back(order[j]);
+                    } else {
+                        waiting++;
+                    }
+                }
+                while (i < b1 && taken[i]) i++;
+                std::stable_partition(cand.begin(), cand.end(), [&](int t) {
+                    for (int k = 0; k < 3; k++)
+                        if (latest[tv[3 * t + k]] <= P + 1 - ref_passes) return true;  // ages out at the next pass
+                    return false;
+                });
+                for (int t : cand) {
+                    batch.push_back(t);
+                    if ((int)batch.size() == 64) emit();
+                }
             }
             if (i >= b1) {
                 if (!batch.empty() || !attached) emit();
@@ -242,6 +340,7 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
             }
             // then the vertices the next triangles miss (not loaded by pass P), first use first
             for (int j = i; j < b1; j++) {
+                if (ahead > 0 && taken[j]) continue;
                 int miss[3], nm = 0;
                 for (int k = 0; k < 3; k++) {
                     const int v = tv[3 * order[j] + k];
@@ -250,7 +349,13 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
                     for (int q = 0; q < nm; q++) dup |= miss[q] == v;
                     if (!dup) miss[nm++] = v;
                 }
-                if ((int)newv.size() + nm > 64) break;
+                if ((int)newv.size() + nm > 64) {
+                    // The pass is chosen up to the first triangle that does not fit.  ahead > 0: its free slots then
+                    // take the vertices of triangles behind that one, as far as they fit: slots that were padding
+                    // spare the next pass as many loads.
+                    if (ahead <= 0 || (int)newv.size() >= 64 || j - i > 2 * ahead) break;
+                    continue;
+                }
                 for (int q = 0; q < nm; q++) {
                     in_new[miss[q]] = 1;
                     newv.push_back(miss[q]);
@@ -274,16 +379,36 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
     }
 }
 
-// Append the streams of one model, from the greedy growth order or the sweep order, whichever needs fewer vertex
-// passes (then fewer steps; ties: the growth order).
+// Append the streams of one model.  The baseline is the greedy growth order or the sweep order, whichever needs fewer
+// vertex passes (then fewer steps; ties: the growth order), with in-order batches.  The same two orders with
+// look-ahead batches (kAhead) and the band orders (three axes, a few band counts) are candidates.  A candidate is
+// eligible when it needs no more passes and no more steps than the baseline, so no mesh ever gets more of either;
+// among the eligible ones the cheapest wins, a vertex pass weighing two steps (about 62 against 30 vector instructions
+// per wave in the fused kernel), the earliest on a tie.  -DPCORE_STREAM_CANDIDATES=0 keeps the baseline (A/B).
+#ifndef PCORE_STREAM_CANDIDATES
+#define PCORE_STREAM_CANDIDATES 1
+#endif
 inline void build_model(const std::vector<int>& tv, const std::vector<float>& vxyz, int tri_base, int num_streams,
                         int vring, int ref_passes, Built& out, int chunks = 4) {
     if (tv.empty()) return;
-    Built a, b;
-    build_model_order(tv, vxyz, locality_order(tv, (int)vxyz.size() / 3), tri_base, num_streams, vring, ref_passes, a,
-                      chunks);
-    build_model_order(tv, vxyz, sweep_order(tv, vxyz), tri_base, num_streams, vring, ref_passes, b, chunks);
-    const Built& w = (b.passes < a.passes || (b.passes == a.passes && b.steps < a.steps)) ? b : a;
+    const std::vector<int> grow = locality_order(tv, (int)vxyz.size() / 3), sweep = sweep_order(tv, vxyz);
+    Built w, b;
+    build_model_order(tv, vxyz, grow, tri_base, num_streams, vring, ref_passes, w, chunks);
+    build_model_order(tv, vxyz, sweep, tri_base, num_streams, vring, ref_passes, b, chunks);
+    if (b.passes < w.passes || (b.passes == w.passes && b.steps < w.steps)) std::swap(w, b);
+#if PCORE_STREAM_CANDIDATES
+    const long long base_passes = w.passes, base_steps = w.steps;
+    auto offer = [&](const std::vector<int>& order) {
+        Built c;
+        build_model_order(tv, vxyz, order, tri_base, num_streams, vring, ref_passes, c, chunks, kAhead);
+        if (c.passes <= base_passes && c.steps <= base_steps && 2 * c.passes + c.steps < 2 * w.passes + w.steps)
+            std::swap(w, c);
+    };
+    offer(grow);
+    offer(sweep);
+    for (int axis = 0; axis < 3; axis++)
+        for (int bands : {1, 2, 3, 4, 6, 8}) offer(band_order(tv, vxyz, axis, bands));
+#endif
     const int step0 = (int)(out.stris.size() / 64), pass0 = (int)(out.sverts.size() / 64);
     out.sverts.insert(out.sverts.end(), w.sverts.begin(), w.sverts.end());
     out.stris.insert(out.stris.end(), w.stris.begin(), w.stris.end());
