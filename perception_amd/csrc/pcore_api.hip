@@ -252,7 +252,8 @@ void build_grid(const std::vector<float4>& pts, float radius, LabelGrid& g, std:
     }
     for (int k = 0; k < 3; k++)
         if (!(lo[k] <= hi[k])) { lo[k] = 0.0f; hi[k] = 0.0f; }
-    // cell >= 2r so a query's radius box touches <= 2 cells per axis; at most 64 cells per axis
+    // cell >= 2.02 r so a query's radius box touches <= 2 cells per axis (process_points writes the bound down); at
+    // most 65 cells per axis: floor(ext / cell) + 1 is 65 when the extent sets the cell and the quotient reaches 64
     const float ext = std::max({hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]});
     float cell = std::max(2.0f * radius * 1.01f, ext / 64.0f);
     if (!(cell > 0.0f)) cell = 1.0f;

@@ -881,7 +881,20 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
     const bool grid_ok = use_seg ? (pl >= 0 && pl < a.num_grids) : true;
     LabelGrid g;
     if (grid_ok) g = a.grids[grid_id];
+    // Radius of the query's box in cells.  A neighbour p within r of q has to fall inside the box by the SAME float
+    // cell coordinate that sorted it into its cell, F(x) = fl(fl(x - o) inv_c).  Per axis |p - q| <= r (1 + 2 eps)
+    // (eps = 2^-24), and with the two roundings of F, each relative eps, F(p) - F(q) <= r inv_c (1 + 3 eps)
+    // + 4 eps (max(|F(p)|, |F(q)|) + 1); the sum fx0 +- rc below rounds once more, 1 eps of its value.  A query with
+    // a neighbour has |F| <= n + 1, so 6 eps (n + 2) = 3.6e-7 (n + 2) cells bound all of it: kBoxRound (n + 2) with
+    // n the grid's longest axis does, 2.8 times over.  With the origin tens of metres from the object (a far observed
+    // point stretches the segment) this term is larger than the 1e-4 r of r_eff, which alone lost neighbours at
+    // r = 0.0075 with the origin 30 m away (tests/nn_cases.py, the stretched cases).
+    // The box still spans <= 2 cells per axis: cells are >= 2.02 r wide, so its width is <= 2 (1.0001 r + 1e-7)
+    // / (2.02 r) + 2 kBoxRound 67 = 0.99020 + 9.9e-8 / r + 1.4e-4 < 1 cell for every r >= 1.1e-5 m (n <= 65).
+    // It only adds candidates to a minimum that the exact d2 <= r2 then tests.
+    constexpr float kBoxRound = 1.0e-6f;
     const float r_eff = sqrtf(a.r2) * 1.0001f + 1e-7f;
+    const float box_rc = grid_ok ? r_eff * g.inv_c + kBoxRound * (float)(max(g.nx, max(g.ny, g.nz)) + 2) : 0.0f;
     int my_bad = 0;
 
     auto process_points = [&](int count) {
@@ -901,7 +914,7 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
                 float best = INFINITY;
                 int bidx = 0x7fffffff;
                 if (grid_ok) {
-                    const float rc = r_eff * g.inv_c;
+                    const float rc = box_rc;
                     const float fx0 = (xp - g.ox) * g.inv_c, fy0 = (yp - g.oy) * g.inv_c, fz0 = (zp - g.oz) * g.inv_c;
                     const float lx = fx0 - rc, hx = fx0 + rc, ly = fy0 - rc, hy = fy0 + rc, lz = fz0 - rc, hz = fz0 + rc;
                     if (hx >= 0.0f && lx < (float)g.nx && hy >= 0.0f && ly < (float)g.ny && hz >= 0.0f && lz < (float)g.nz) {
