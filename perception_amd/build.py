@@ -44,7 +44,7 @@ def kernel_source_digest() -> str:
     import hashlib
 
     h = hashlib.sha256(" ".join(flags()).encode())  # the compile flags too: a profile is of one build
-    for f in ("pcore_kernels.hip", "pcore_internal.h", "pcore_cov.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h"):
+    for f in ("pcore_kernels.hip", "pcore_internal.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h"):
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

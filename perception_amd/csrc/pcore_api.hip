@@ -84,11 +84,8 @@ struct pcore_ctx {
     DevBuf<int32_t> scratch_dc_pre;  // stage CLOUD result_dc_index: per-pose sample prefixes
     DevBuf<int32_t> icp_corr_hist;  // GicpArgs::corr_hist
     DevBuf<double> icp_mahal;   // GicpArgs::mahal
-    DevBuf<int32_t> icp_counter;
-    DevBuf<unsigned long long> icp_iter_stats;  // GicpArgs::iter_stats ([0..3]) and help_stats ([4..7]), zeroed per call
-    DevBuf<unsigned> icp_help_ctl;              // GicpArgs::help_ctl (zeroed per launch by launch_gicp)
-    DevBuf<unsigned long long> icp_help_gran;   // GicpArgs::help_gran
-    uint32_t icp_help_tag = 0;                  // GicpArgs::help_tag of the last launch (1..0xFFFF, cycling)
+    DevBuf<int32_t> icp_counter;                // GicpArgs::work_counter
+    DevBuf<unsigned long long> icp_iter_stats;  // GicpArgs::iter_stats ([0..3]), zeroed per call
     // their copy in pinned host memory, made on the call's stream before each chunk's end event (pcore_get_stats reads
     // it after that event: no synchronous copy, which would wait for every blocking stream of the device)
     unsigned long long* icp_iter_stats_host = nullptr;
@@ -343,7 +340,7 @@ void pcore_destroy(pcore_ctx* c) {
     (void)dev_free(c->scratch_counts); (void)dev_free(c->scratch_offsets); (void)dev_free(c->scratch_total);
     (void)dev_free(c->tgt); (void)dev_free(c->seg_lo); (void)dev_free(c->seg_hi); (void)dev_free(c->seg_cnt); (void)dev_free(c->tgt_quads); (void)dev_free(c->seg_qoff);
     (void)dev_free(c->tgt_cov_label); (void)dev_free(c->tgt_cov_all);
-    (void)dev_free(c->icp_cloud); (void)dev_free(c->icp_count); (void)dev_free(c->icp_cov); (void)dev_free(c->icp_corr); (void)dev_free(c->icp_corr_hist); (void)dev_free(c->scratch_dc_pre); (void)dev_free(c->icp_mahal); (void)dev_free(c->icp_counter); (void)dev_free(c->icp_iter_stats); (void)dev_free(c->icp_help_ctl); (void)dev_free(c->icp_help_gran); (void)dev_free(c->icp_order_keys); (void)dev_free(c->icp_order_idx); (void)dev_free(c->icp_order_temp);
+    (void)dev_free(c->icp_cloud); (void)dev_free(c->icp_count); (void)dev_free(c->icp_cov); (void)dev_free(c->icp_corr); (void)dev_free(c->icp_corr_hist); (void)dev_free(c->scratch_dc_pre); (void)dev_free(c->icp_mahal); (void)dev_free(c->icp_counter); (void)dev_free(c->icp_iter_stats); (void)dev_free(c->icp_order_keys); (void)dev_free(c->icp_order_idx); (void)dev_free(c->icp_order_temp);
     (void)dev_free(c->stri_orig); (void)dev_free(c->tri_lab); (void)dev_free(c->obs_lab); (void)dev_free(c->colour_id);
     (void)dev_free(c->metric_part); (void)dev_free(c->tri_rgb); (void)dev_free(c->render_tri);
     (void)dev_free(c->planar_cell_start); (void)dev_free(c->planar_pts);
@@ -683,6 +680,82 @@ int pcore_set_observation(pcore_ctx* c, const int32_t* d_src_depth_cm, const uin
     return PCORE_OK;
 }
 
+namespace {
+
+// The checks of a call that rasters the image sampled at `stride`, `who` prefixing the messages: the stride divides the
+// width, the sampled image (ws x hs, returned) fits the kernels' 12-bit sample coordinates and, whole, a workgroup's LDS
+// (the overflow launch; `colour`: with the colour gate's tile).  `lds_hint` ends the LDS message; `need` appends the
+// bytes it would take.
+int check_sampling(pcore_ctx* c, const std::string& who, int stride, bool colour, const char* lds_hint, bool need,
+                   int& ws, int& hs) {
+    const int W = c->cam.width, H = c->cam.height;
+    if (stride <= 0 || W % stride != 0) return fail(c, PCORE_E_INVALID_ARG, who + ": width must be a multiple of stride");
+    ws = W / stride;
+    hs = (H + stride - 1) / stride;
+    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, who + ": sampled image too large");
+    const size_t lds = fused_lds_bytes(ws * hs, c->bitmap_words, colour);
+    if (lds > (size_t)c->prop.sharedMemPerBlock)
+        return fail(c, PCORE_E_INVALID_ARG, who + ": sampled z-buffer does not fit in LDS" + lds_hint +
+                                                (need ? "; need " + std::to_string(lds) + " B" : std::string()));
+    return PCORE_OK;
+}
+
+// Equal chunks of a batch whose poses each take `per_pose` bytes of scratch, as few as the budget allows (every chunk
+// ends with the tail of its slowest pose): min(32 GiB, max(1 GiB, 40 % of the free device memory)), or what the
+// caller's environment knob sets (test / A/B; at least 1, in units of 2^knob_shift bytes).
+struct Chunks {
+    int chunk, nchunks;
+};
+Chunks plan_chunks(int num_poses, size_t per_pose, const char* knob, int knob_shift) {
+    size_t budget = (size_t)32 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+        budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
+    if (const char* e = getenv(knob)) budget = (size_t)std::max(1LL, atoll(e)) << knob_shift;
+    const int max_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_pose), 0x7fffffff);
+    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
+    return {(num_poses + nchunks - 1) / nchunks, nchunks};
+}
+
+// A stream whose capture state cannot be queried (hipStreamIsCapturing fails, e.g. on the legacy stream while another
+// stream captures in global mode) counts as capturing.
+bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return cap != hipStreamCaptureStatusNone;
+}
+
+// `what` (or the scratch) has to be built or allocated first: none of it may happen while the stream captures
+int refuse_setup_in_capture(pcore_ctx* c, const char* who, const char* what, bool setup, hipStream_t s) {
+    if (setup && stream_capturing(s))
+        return fail(c, PCORE_E_STATE, std::string(who) + ": " + what + " or the scratch would have to be built while the "
+                                      "stream captures; run the call once before the capture");
+    return PCORE_OK;
+}
+
+// Stage CLOUD of n poses into per-pose slots of the whole sampled image (render_cloud_kernel; `a` from fill_fused_args),
+// rastered through the fused launch's most-occupied tile (6 workgroups per CU; larger windows in chunks of it).
+// PCORE_FUSED_TCAP (test knob): a tile of that many samples.
+hipError_t stage_clouds(pcore_ctx* c, FusedArgs& a, const float* d_poses, const int32_t* d_pose_model,
+                        const int32_t* d_pose_label, int n, float4* cloud_out, int32_t* cloud_count, hipStream_t s) {
+    a.poses = d_poses;
+    a.pose_model = d_pose_model;
+    a.pose_label = d_pose_label;
+    a.num_poses = n;
+    a.cloud_out = cloud_out;
+    a.cloud_count = cloud_count;
+    a.cloud_cap = a.ws * a.hs;
+    a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
+    if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
+    if (a.tcap <= 0) a.tcap = a.ws * a.hs;
+    return launch_render_cloud(a, s);
+}
+
+}  // namespace
+
 // the tier with the most workgroups per CU whose tile holds the windows of >= 99 % of the histogram's poses
 static int choose_tier(const int32_t* h, const int* edge, int fallback) {
     long long tot = 0;
@@ -719,15 +792,8 @@ static hipError_t set_fused_tiles(pcore_ctx* c, int num_poses, FusedArgs& a, hip
         if ((e = hipMemset(c->win_hist.p, 0, 2 * (kTileTiers + 1) * sizeof(int32_t))) != hipSuccess) return e;
     }
     // A captured launch counts into buffers of its own that nothing publishes or reads: its replays can
-    // never add to the parity histograms the eager launches publish.  A stream whose capture state cannot be queried
-    // (hipStreamIsCapturing fails, e.g. on the legacy stream while another stream captures in global mode) is treated
-    // as capturing: no window probe, no feedback.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) {
-        (void)hipGetLastError();
-        cap = hipStreamCaptureStatusActive;
-    }
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    // never add to the parity histograms the eager launches publish: no window probe, no feedback.
+    const bool capturing = stream_capturing(s);
     int edge[kTileTiers];
     for (int t = 0; t < kTileTiers; t++) edge[t] = fused_tier_samples(t, a.ws, a.hs, a.bitmap_words, colour, c->dinfo);
     const long long key = (((long long)a.ws * 4096 + a.hs) * 65536 + a.bitmap_words) * 2 + (colour ? 1 : 0);
@@ -809,19 +875,12 @@ static int validate_eval(pcore_ctx* c, const char* who, const float* d_poses, co
         return fail(c, PCORE_E_INVALID_ARG, w + ": cost_type 2 needs pose labels and a source mask");
     if (p->calc_obs_cost && (!d_pose_obs_total || !d_out_oc || !d_out_diff))
         return fail(c, PCORE_E_INVALID_ARG, w + ": calc_obs_cost needs pose_obs_total and oc/diff outputs");
-    const int W = c->cam.width, H = c->cam.height;
-    if (p->stride <= 0 || W % p->stride != 0)
-        return fail(c, PCORE_E_INVALID_ARG, w + ": width must be a multiple of stride");
-    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
-    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, w + ": sampled image too large");
     // the overflow launch holds the whole sampled image in LDS (the GICP cloud launch needs less: no bitmap)
-    const size_t lds = fused_lds_bytes(ws * hs, c->bitmap_words, p->cost_type == PCORE_COST_RGBD_3DOF);
-    if (lds > (size_t)c->prop.sharedMemPerBlock)
-        return fail(c, PCORE_E_INVALID_ARG,
-                    w + ": sampled z-buffer does not fit in LDS (use a larger stride); need " + std::to_string(lds) +
-                        " B");
-    return PCORE_OK;
+    int ws, hs;
+    return check_sampling(c, w, p->stride, p->cost_type == PCORE_COST_RGBD_3DOF, " (use a larger stride)", true, ws, hs);
 }
+
+static int fill_fused_args(pcore_ctx* c, const pcore_eval_params* p, FusedArgs& a);  // below
 
 static int evaluate_impl(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
                          const float* d_pose_obs_total, int32_t num_poses, const pcore_eval_params* p, float* d_out_rc,
@@ -831,47 +890,18 @@ static int evaluate_impl(pcore_ctx* c, const float* d_poses, const int32_t* d_po
     const int vr = validate_eval(c, "evaluate", d_poses, d_pose_model, d_pose_label, d_pose_obs_total, num_poses, p,
                                  d_out_rc, d_out_oc, d_out_diff);
     if (vr != PCORE_OK || num_poses == 0) return vr;
-    const int W = c->cam.width, H = c->cam.height;
-    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = ensure_sampled(c, p->stride, s);
     if (rc != PCORE_OK) return rc;
 
     FusedArgs a{};
+    fill_fused_args(c, p, a);
     a.poses = d_poses;
     a.pose_model = d_pose_model;
     a.pose_label = (p->cost_type == PCORE_COST_DEPTH_6DOF) ? d_pose_label : nullptr;
     a.pose_obs_total = d_pose_obs_total;
     a.num_poses = num_poses;
-    a.sverts = c->sverts.p;
-    a.stris = c->stris.p;
-    a.streams = c->streams.p;
-    a.model_st_lo = c->model_st_lo.p;
-    a.model_st_hi = c->model_st_hi.p;
-    a.model_box = c->model_box.p;
-    a.num_models = c->num_models;
-    const float* pj = c->cam.proj;
-    a.p00 = pj[0]; a.p01 = pj[1]; a.p02 = pj[2]; a.p03 = pj[3];
-    a.p10 = pj[4]; a.p11 = pj[5]; a.p12 = pj[6]; a.p13 = pj[7];
-    a.proj_sparse = (pj[1] == 0.0f && pj[3] == 0.0f && pj[4] == 0.0f && pj[7] == 0.0f) ? 1 : 0;
-    a.width = W;
-    a.height = H;
-    a.stride = p->stride;
-    a.ws = ws;
-    a.hs = hs;
-    a.cx = c->cam.cx; a.cy = c->cam.cy; a.fx = c->cam.fx; a.fy = c->cam.fy;
-    a.depth_factor = p->depth_factor;
-    a.src_s = c->src_s.p;
-    a.lab_s = c->lab_s.p;
-    a.grids = c->grids.p;
-    a.cell_start = c->cell_start.p;
-    a.grid_pts = c->grid_pts.p;
-    a.num_grids = c->num_grids;
-    a.bitmap_words = c->bitmap_words;
-    a.r2 = p->sensor_resolution * p->sensor_resolution;  // renderer.cu:1877
-    a.occlusion_threshold = p->occlusion_threshold;
-    a.calc_obs = p->calc_obs_cost;
     a.out_rc = d_out_rc;
     a.out_oc = d_out_oc;
     a.out_diff = d_out_diff;
@@ -881,7 +911,7 @@ static int evaluate_impl(pcore_ctx* c, const float* d_poses, const int32_t* d_po
         a.tri_lab = c->tri_lab.p;
         a.obs_lab = c->obs_lab.p;
         a.colour_thr = p->color_distance_threshold;
-        HIPC(c, reserve_gen(c, c->colour_id, (size_t)num_poses * ws * hs));
+        HIPC(c, reserve_gen(c, c->colour_id, (size_t)num_poses * a.ws * a.hs));
         a.cid = c->colour_id.p;
     }
     if (const char* e = getenv("PCORE_DEBUG_SKIP")) a.dbg_skip = atoi(e);
@@ -911,6 +941,7 @@ int pcore_evaluate_select(pcore_ctx* c, const float* d_poses, const int32_t* d_p
                          d_out_diff, nullptr, d_keys, index_base, num_models, stream);
 }
 
+// a launch's FusedArgs but for its batch and outputs: the mesh, the camera, the sampled observation, the cost settings
 static int fill_fused_args(pcore_ctx* c, const pcore_eval_params* p, FusedArgs& a) {
     const int W = c->cam.width, H = c->cam.height;
     const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
@@ -970,41 +1001,26 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     int rc = ensure_sampled(c, p->stride, s);
     if (rc != PCORE_OK) return rc;
     const int k = ip->k_correspondences;
-    // target covariances, once per (observation, k)
+    // target covariances, once per (observation, k): of the nl label segments (6-DoF) or of the whole cloud, segment nl
     const int nl = c->num_grids;
-    if (six && c->cov_k_label != k) {
-        HIPC(c, dev_reserve(c->tgt_cov_label, (size_t)6 * std::max(c->num_obs, 1)));
-        HIPC(c, launch_covariances(c->tgt.p, c->seg_lo.p, c->seg_cnt.p, 0, nl, k, c->tgt_cov_label.p, s, kGridNNMin));
-        HIPC(c, launch_covariances_grid(c->tgt.p, c->seg_lo_h.data(), c->seg_cnt_h.data(), nl, 0, c->grids.p,
-                                        c->cell_start.p, c->grid_pts.p, k, c->tgt_cov_label.p, s));
-        c->cov_k_label = k;
-    }
-    if (!six && c->cov_k_all != k) {
-        HIPC(c, dev_reserve(c->tgt_cov_all, (size_t)6 * std::max(c->num_obs, 1)));
-        HIPC(c, launch_covariances(c->tgt.p, c->seg_lo.p + nl, c->seg_cnt.p + nl, 0, 1, k, c->tgt_cov_all.p, s,
-                                   kGridNNMin));
-        HIPC(c, launch_covariances_grid(c->tgt.p, c->seg_lo_h.data() + nl, c->seg_cnt_h.data() + nl, 1, nl, c->grids.p,
-                                        c->cell_start.p, c->grid_pts.p, k, c->tgt_cov_all.p, s));
-        c->cov_k_all = k;
+    DevBuf<double>& tcov = six ? c->tgt_cov_label : c->tgt_cov_all;
+    int& tcov_k = six ? c->cov_k_label : c->cov_k_all;
+    if (tcov_k != k) {
+        const int seg0 = six ? 0 : nl, nseg = six ? nl : 1;
+        HIPC(c, dev_reserve(tcov, (size_t)6 * std::max(c->num_obs, 1)));
+        HIPC(c, launch_covariances(c->tgt.p, c->seg_lo.p + seg0, c->seg_cnt.p + seg0, 0, nseg, k, tcov.p, s, kGridNNMin));
+        HIPC(c, launch_covariances_grid(c->tgt.p, c->seg_lo_h.data() + seg0, c->seg_cnt_h.data() + seg0, nseg, seg0,
+                                        c->grids.p, c->cell_start.p, c->grid_pts.p, k, tcov.p, s));
+        tcov_k = k;
     }
     const int nsamp = ws * hs;
     // GICP scratch per pose: nsamp cloud slots (16 B) + covariances (48 B) + the iteration's correspondences (4 B)
     // and Mahalanobis matrices (48 B).  Chunks are as large as the budget below allows and equal in size: every
     // chunk ends with the tail of its slowest pose, so fewer chunks mean fewer tails.
     const size_t per_pose = (size_t)nsamp * 116 + (size_t)kCorrHist * std::min(nsamp, kCorrHistCap) * 4;
-    // Up to 32 GiB (and at most 40 % of the free HBM): one chunk for 100k poses at 640x480 / stride 8.
-    // Each chunk ends with the tail of its slowest pose, so on C3 (50k poses) one chunk instead of two
-    // saves ~5 ms of a 37 ms step.
-    size_t budget = (size_t)32 << 30;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-            budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
-    }
-    if (const char* e = getenv("PCORE_ICP_SCRATCH_GIB")) budget = (size_t)std::max(1, atoi(e)) << 30;  // A/B knob
-    const int max_chunk = (int)std::max<size_t>(1, budget / per_pose);
-    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
-    const int chunk = (num_poses + nchunks - 1) / nchunks;
+    // Up to 32 GiB (and at most 40 % of the free HBM): one chunk for 100k poses at 640x480 / stride 8; on C3 (50k poses)
+    // one chunk instead of two saves ~5 ms of a 37 ms step.
+    const auto [chunk, nchunks] = plan_chunks(num_poses, per_pose, "PCORE_ICP_SCRATCH_GIB", 30);
     HIPC(c, dev_reserve(c->icp_cloud, (size_t)chunk * nsamp));
     HIPC(c, dev_reserve(c->icp_count, (size_t)chunk));
     HIPC(c, dev_reserve(c->icp_cov, (size_t)6 * chunk * nsamp));
@@ -1015,19 +1031,10 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     const bool use_hist = !getenv("PCORE_GICP_NO_HIST");  // A/B knob (same results)
     if (use_hist) HIPC(c, dev_reserve(c->icp_corr_hist, (size_t)chunk * kCorrHist * hist_cap));
     HIPC(c, dev_reserve(c->icp_mahal, (size_t)6 * chunk * nsamp));
-    HIPC(c, dev_reserve(c->icp_counter, 4));  // [0] one-wave queue, [1] heavy queue, [2] heavy poses
-    HIPC(c, dev_reserve(c->icp_iter_stats, 8));
+    HIPC(c, dev_reserve(c->icp_counter, 1));
+    HIPC(c, dev_reserve(c->icp_iter_stats, 4));
     if (!c->icp_iter_stats_host)
-        HIPC(c, hipHostMalloc((void**)&c->icp_iter_stats_host, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    // the GICP help board (a -DPCORE_GICP_HELP_BOARD=1 build): a slot per resident wave, at most 512 MiB of granules
-    // (PCORE_GICP_HELP=0: no help, A/B)
-    int help_slots = 0;
-    if (kGicpHelpBoard && !(getenv("PCORE_GICP_HELP") && atoi(getenv("PCORE_GICP_HELP")) == 0)) {
-        const size_t per_slot = (size_t)(kHelpXfGranules + nsamp) * sizeof(unsigned long long);
-        help_slots = (int)std::min<size_t>((size_t)std::max(1, c->dinfo.gicp_resident_wgs), ((size_t)512 << 20) / per_slot);
-        HIPC(c, dev_reserve(c->icp_help_ctl, help_ctl_words(help_slots)));
-        HIPC(c, dev_reserve(c->icp_help_gran, (size_t)help_slots * (kHelpXfGranules + nsamp)));
-    }
+        HIPC(c, hipHostMalloc((void**)&c->icp_iter_stats_host, 4 * sizeof(unsigned long long), hipHostMallocDefault));
     HIPC(c, dev_reserve(c->icp_order_keys, (size_t)2 * chunk));
     HIPC(c, dev_reserve(c->icp_order_idx, (size_t)2 * chunk));
     const size_t order_temp = gicp_order_temp_bytes(chunk);
@@ -1044,7 +1051,7 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     HIPC(c, hipStreamIsCapturing(s, &cap_status));
     const bool timed = cap_status == hipStreamCaptureStatusNone;
     c->icp_ev_used = 0;
-    HIPC(c, hipMemsetAsync(c->icp_iter_stats.p, 0, 8 * sizeof(unsigned long long), s));
+    HIPC(c, hipMemsetAsync(c->icp_iter_stats.p, 0, 4 * sizeof(unsigned long long), s));
     while (timed && c->icp_ev.size() < (size_t)3 * nchunks) {
         hipEvent_t e;
         HIPC(c, hipEventCreate(&e));
@@ -1060,7 +1067,7 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     g.corr_hist_cap = hist_cap;
     g.src_cap = nsamp;
     g.tgt = c->tgt.p;
-    g.tgt_cov = six ? c->tgt_cov_label.p : c->tgt_cov_all.p;
+    g.tgt_cov = tcov.p;
     g.seg_lo = c->seg_lo.p;
     g.seg_hi = c->seg_hi.p;
     g.num_segs = nl;
@@ -1073,20 +1080,8 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     g.rot_eps = ip->rotation_epsilon;
     g.trans_eps = ip->transformation_epsilon;
     g.work_counter = c->icp_counter.p;
-    g.heavy_counter = c->icp_counter.p + 1;
-    g.heavy_count = c->icp_counter.p + 2;
-    // heavy poses (a -DPCORE_GICP_WG_WAVES=4 build only): source points x targets >= 60,000 (e.g. 211 points on a
-    // 285-target segment), at most 2 per CU; PCORE_GICP_HEAVY_COST / PCORE_GICP_HEAVY_MAX for A/B (0: none)
-    g.heavy_cost = kGicpHeavyBuild ? 60000 : 0;
-    g.heavy_max = 2 * std::max(1, c->dinfo.num_cus);
-    if (const char* e = getenv("PCORE_GICP_HEAVY_COST")) g.heavy_cost = atoll(e);
-    if (const char* e = getenv("PCORE_GICP_HEAVY_MAX")) g.heavy_max = atoi(e);
     g.cycle_window = ip->cycle_exit_window;
     g.iter_stats = c->icp_iter_stats.p;
-    g.help_ctl = help_slots > 0 ? c->icp_help_ctl.p : nullptr;
-    g.help_gran = help_slots > 0 ? c->icp_help_gran.p : nullptr;
-    g.help_stats = c->icp_iter_stats.p + 4;
-    g.help_slots = help_slots;
     g.tgt_quads = c->tgt_quads.p;
     g.seg_qoff = c->seg_qoff.p;
     g.grids = c->grids.p;
@@ -1104,58 +1099,28 @@ int pcore_evaluate_icp(pcore_ctx* c, const float* d_poses, const int32_t* d_pose
     }
     for (int base = 0; base < num_poses; base += chunk) {
         const int n = std::min(chunk, num_poses - base);
-        a.poses = d_poses + (size_t)16 * base;
-        a.pose_model = d_pose_model + base;
-        a.pose_label = six ? d_pose_label + base : nullptr;
-        a.num_poses = n;
-        a.cloud_out = c->icp_cloud.p;
-        a.cloud_count = c->icp_count.p;
-        a.cloud_cap = nsamp;
-        // the fused launch's most-occupied tile (6 workgroups per CU); larger windows are rastered in chunks of it
-        a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
-        if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
-        if (a.tcap <= 0) a.tcap = a.ws * a.hs;
-        // the source covariances in a launch of their own, or (PCORE_COV_FOLD=1, A/B) in render_cloud's launch; either
-        // way bit-identical (pcore_cov.h).  Folded, the C3 step took 13.70 / 13.75 ms against 12.74 / 12.95 ms
-        // (profiles/r06g/): render_cloud's workgroups hold their raster LDS (6 per CU) through the k-NN rounds, where
-        // the covariance launch runs 32 one-wave workgroups per CU.
-        const bool fold = k == 10 && getenv("PCORE_COV_FOLD") && atoi(getenv("PCORE_COV_FOLD")) == 1;
-        a.cloud_cov = fold ? c->icp_cov.p : nullptr;
-        // PCORE_COV_GICP=1: the covariances in gicp_kernel's pose prologue instead (launch_gicp runs the covariance
-        // launch itself when it picks a kernel without the prologue); bit-identical
-        const bool gfold = !fold && k == 10 && !getenv("PCORE_COV_BRUTE") && getenv("PCORE_COV_GICP") &&
-                           atoi(getenv("PCORE_COV_GICP")) == 1;
-        g.cov_fold = gfold ? c->icp_cov.p : nullptr;
-        g.cov_fx = a.fx;
-        g.cov_fy = a.fy;
-        g.cov_cx = a.cx;
-        g.cov_cy = a.cy;
-        g.cov_stride = p->stride;
         hipEvent_t* ev = timed ? c->icp_ev.data() + 3 * c->icp_ev_used : nullptr;
-        if (ev && fold) HIPC(c, hipEventRecord(ev[0], s));  // icp_runtime then spans the cloud + covariance launch
-        HIPC(c, launch_render_cloud(a, s));
-        if (ev && !fold) HIPC(c, hipEventRecord(ev[0], s));
-        // the clouds' covariances: k = 10 by the threshold k-NN over each cloud's sample grid (pcore_cov.h;
-        // PCORE_COV_BRUTE=1 restores the brute-force kernel for A/B), other k by the brute force; bit-identical
-        if (!fold && !gfold && k == 10 && !getenv("PCORE_COV_BRUTE"))
+        HIPC(c, stage_clouds(c, a, d_poses + (size_t)16 * base, d_pose_model + base,
+                             six ? d_pose_label + base : nullptr, n, c->icp_cloud.p, c->icp_count.p, s));
+        if (ev) HIPC(c, hipEventRecord(ev[0], s));
+        // the clouds' covariances: k = 10 by the threshold k-NN over each cloud's sample grid (pcore_cov.h), other k
+        // by the brute force; bit-identical
+        if (k == 10)
             HIPC(c, launch_covariances_cloud(c->icp_cloud.p, c->icp_count.p, nsamp, n, a.fx, a.fy, a.cx, a.cy, p->stride,
                                              c->icp_cov.p, s));
-        else if (!fold && !gfold)
+        else
             HIPC(c, launch_covariances(c->icp_cloud.p, nullptr, c->icp_count.p, nsamp, n, k, c->icp_cov.p, s));
         g.pose_base = base;
         g.pose_order = nullptr;
-        HIPC(c, hipMemsetAsync(g.heavy_count, 0, sizeof(int32_t), s));
         if (!getenv("PCORE_GICP_INDEX_ORDER")) {  // A/B knob: the queue in index order
             HIPC(c, launch_gicp_order(g, n, c->icp_order_keys.p, c->icp_order_keys.p + chunk, c->icp_order_idx.p,
                                       c->icp_order_idx.p + chunk, c->icp_order_temp.p, order_temp, s));
             g.pose_order = c->icp_order_idx.p + chunk;
         }
-        c->icp_help_tag = c->icp_help_tag % 0xFFFFu + 1u;  // a new tag for every launch on this context's board
-        g.help_tag = c->icp_help_tag;
         if (ev) HIPC(c, hipEventRecord(ev[1], s));
         HIPC(c, launch_gicp(g, n, c->dinfo, s, grid_needed));
         if (ev)  // the counters so far (the last chunk's copy holds the call's totals)
-            HIPC(c, hipMemcpyAsync(c->icp_iter_stats_host, c->icp_iter_stats.p, 8 * sizeof(unsigned long long),
+            HIPC(c, hipMemcpyAsync(c->icp_iter_stats_host, c->icp_iter_stats.p, 4 * sizeof(unsigned long long),
                                    hipMemcpyDeviceToHost, s));
         if (ev) {
             HIPC(c, hipEventRecord(ev[2], s));
@@ -1189,44 +1154,22 @@ int pcore_icp_planar(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_m
         if (!std::isfinite(world_from_cam[i])) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: non-finite world_from_cam");
     if (num_poses < 0 || (num_poses > 0 && (!d_poses || !d_pose_model || !d_out_xform || !d_out_iters || !d_out_status)))
         return fail(c, PCORE_E_INVALID_ARG, "icp_planar: null pose / output pointer");
-    const int W = c->cam.width, H = c->cam.height;
-    if (p->stride <= 0 || W % p->stride != 0)
-        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: width must be a multiple of stride");
-    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
-    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "icp_planar: sampled image too large");
-    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
-        return fail(c, PCORE_E_INVALID_ARG, "icp_planar: sampled z-buffer does not fit in LDS (use a larger stride)");
+    int ws, hs;
+    if (const int vr = check_sampling(c, "icp_planar", p->stride, false, " (use a larger stride)", false, ws, hs)) return vr;
     if (num_poses == 0) return PCORE_OK;
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int nsamp = ws * hs;
-    // chunks by the scratch budget, as pcore_evaluate_icp: a slot of nsamp points (16 B) and a count per pose, at most
-    // min(32 GiB, 40 % of the free device memory); PCORE_ICP2D_SCRATCH_BYTES sets the budget (test / A/B knob)
-    const size_t per_pose = (size_t)nsamp * sizeof(float4) + sizeof(int32_t);
-    size_t budget = (size_t)32 << 30;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-            budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
-    }
-    if (const char* e = getenv("PCORE_ICP2D_SCRATCH_BYTES")) budget = (size_t)std::max(1LL, atoll(e));
-    const int max_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_pose), 0x7fffffff);
-    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
-    const int chunk = (num_poses + nchunks - 1) / nchunks;
-    // what has to be built or allocated first; none of it may happen while the stream captures
+    // chunks by the scratch budget, as pcore_evaluate_icp: a slot of nsamp points (16 B) and a count per pose
+    const int chunk = plan_chunks(num_poses, (size_t)nsamp * sizeof(float4) + sizeof(int32_t),
+                                  "PCORE_ICP2D_SCRATCH_BYTES", 0).chunk;
+    // what has to be built or allocated first
     const bool grid_stale = c->planar_obs_serial != c->obs_serial ||
                             std::memcmp(c->planar_m, world_from_cam, sizeof(c->planar_m)) != 0 ||
                             std::memcmp(&c->planar_radius, &pp->max_correspondence, sizeof(float)) != 0;
     const bool setup = grid_stale || c->sampled_stride != p->stride || !c->icp_cloud.p || !c->icp_count.p ||
                        c->icp_cloud.n < (size_t)chunk * nsamp || c->icp_count.n < (size_t)chunk;
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap_status) != hipSuccess) {
-        (void)hipGetLastError();
-        cap_status = hipStreamCaptureStatusActive;
-    }
-    if (setup && cap_status != hipStreamCaptureStatusNone)
-        return fail(c, PCORE_E_STATE, "icp_planar: the world-frame grid or the scratch would have to be built while the "
-                                      "stream captures; run the call once before the capture");
+    if (const int cr = refuse_setup_in_capture(c, "icp_planar", "the world-frame grid", setup, s)) return cr;
     if (grid_stale) {
         const int n = (int)(c->obs_xyz_h.size() / 3);
         std::vector<float4> wp((size_t)n);
@@ -1277,17 +1220,8 @@ int pcore_icp_planar(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_m
     g.out_mse = d_out_mse;
     for (int base = 0; base < num_poses; base += chunk) {
         const int n = std::min(chunk, num_poses - base);
-        a.poses = d_poses + (size_t)16 * base;
-        a.pose_model = d_pose_model + base;
-        a.pose_label = nullptr;
-        a.num_poses = n;
-        a.cloud_out = c->icp_cloud.p;
-        a.cloud_count = c->icp_count.p;
-        a.cloud_cap = nsamp;
-        a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
-        if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
-        if (a.tcap <= 0) a.tcap = a.ws * a.hs;
-        HIPC(c, launch_render_cloud(a, s));
+        HIPC(c, stage_clouds(c, a, d_poses + (size_t)16 * base, d_pose_model + base, nullptr, n, c->icp_cloud.p,
+                             c->icp_count.p, s));
         g.pose_base = base;
         HIPC(c, launch_planar_icp(g, n, s));
     }
@@ -1345,33 +1279,19 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
         return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: null pose / output pointer");
     if (d_pose_label && !c->obs_has_mask)
         return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: pose labels need a source mask");
-    const int W = c->cam.width, H = c->cam.height;
-    if (p->stride <= 0 || W % p->stride != 0)
-        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: width must be a multiple of stride");
-    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
-    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: sampled image too large");
-    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
-        return fail(c, PCORE_E_INVALID_ARG,
-                    "icp_point2plane: sampled z-buffer does not fit in LDS (use a larger stride)");
+    int ws, hs;
+    if (const int vr = check_sampling(c, "icp_point2plane", p->stride, false, " (use a larger stride)", false, ws, hs))
+        return vr;
     if (num_poses == 0) return PCORE_OK;
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const int nsamp = ws * hs;
-    // chunks by the scratch budget, as pcore_icp_planar: a slot of nsamp points (16 B) and a count per pose, at most
-    // min(32 GiB, 40 % of the free device memory); PCORE_P2P_SCRATCH_BYTES sets the budget (test / A/B knob)
-    const size_t per_pose = (size_t)nsamp * sizeof(float4) + sizeof(int32_t);
-    size_t budget = (size_t)32 << 30;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-            budget = std::min(budget, std::max<size_t>((size_t)1 << 30, free_b / 5 * 2));
-    }
-    if (const char* e = getenv("PCORE_P2P_SCRATCH_BYTES")) budget = (size_t)std::max(1LL, atoll(e));
-    const int max_chunk = (int)std::min<size_t>(std::max<size_t>(1, budget / per_pose), 0x7fffffff);
-    const int nchunks = (num_poses + max_chunk - 1) / max_chunk;
-    const int chunk = (num_poses + nchunks - 1) / nchunks;
-    // what has to be built or allocated first; none of it may happen while the stream captures
+    // chunks by the scratch budget, as pcore_icp_planar: a slot of nsamp points (16 B) and a count per pose
+    const int chunk = plan_chunks(num_poses, (size_t)nsamp * sizeof(float4) + sizeof(int32_t),
+                                  "PCORE_P2P_SCRATCH_BYTES", 0).chunk;
+    // what has to be built or allocated first
     const pcore_camera& cam = c->cam;
+    const int W = cam.width, H = cam.height;
     const bool scene_stale = c->p2p_obs_serial != c->obs_serial || c->p2p_cam.width != W || c->p2p_cam.height != H ||
                              std::memcmp(&c->p2p_cam.fx, &cam.fx, sizeof(float)) != 0 ||
                              std::memcmp(&c->p2p_cam.fy, &cam.fy, sizeof(float)) != 0 ||
@@ -1379,14 +1299,7 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
                              std::memcmp(&c->p2p_cam.cy, &cam.cy, sizeof(float)) != 0;
     const bool setup = scene_stale || c->sampled_stride != p->stride || !c->icp_cloud.p || !c->icp_count.p ||
                        c->icp_cloud.n < (size_t)chunk * nsamp || c->icp_count.n < (size_t)chunk;
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap_status) != hipSuccess) {
-        (void)hipGetLastError();
-        cap_status = hipStreamCaptureStatusActive;
-    }
-    if (setup && cap_status != hipStreamCaptureStatusNone)
-        return fail(c, PCORE_E_STATE, "icp_point2plane: the scene or the scratch would have to be built while the "
-                                      "stream captures; run the call once before the capture");
+    if (const int cr = refuse_setup_in_capture(c, "icp_point2plane", "the scene", setup, s)) return cr;
     if (scene_stale) {
         const size_t npx = (size_t)W * H;
         HIPC(c, hipStreamSynchronize(s));  // an earlier call on the stream may still read the old scene
@@ -1426,17 +1339,8 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
     g.out_iters = d_out_iters;
     for (int base = 0; base < num_poses; base += chunk) {
         const int n = std::min(chunk, num_poses - base);
-        a.poses = d_poses + (size_t)16 * base;
-        a.pose_model = d_pose_model + base;
-        a.pose_label = d_pose_label ? d_pose_label + base : nullptr;
-        a.num_poses = n;
-        a.cloud_out = c->icp_cloud.p;
-        a.cloud_count = c->icp_count.p;
-        a.cloud_cap = nsamp;
-        a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
-        if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
-        if (a.tcap <= 0) a.tcap = a.ws * a.hs;
-        HIPC(c, launch_render_cloud(a, s));
+        HIPC(c, stage_clouds(c, a, d_poses + (size_t)16 * base, d_pose_model + base,
+                             d_pose_label ? d_pose_label + base : nullptr, n, c->icp_cloud.p, c->icp_count.p, s));
         g.pose_base = base;
         HIPC(c, launch_p2p_icp(g, n, s));
     }
@@ -1485,13 +1389,8 @@ int pcore_debug_render_clouds(pcore_ctx* c, const float* d_poses, const int32_t*
         return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: null pose / output pointer");
     if (d_pose_label && !c->obs_has_mask)
         return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: pose labels need a source mask");
-    const int W = c->cam.width, H = c->cam.height;
-    if (p->stride <= 0 || W % p->stride != 0)
-        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: width must be a multiple of stride");
-    const int ws = W / p->stride, hs = (H + p->stride - 1) / p->stride;
-    if (ws > 4095 || hs > 4095) return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: sampled image too large");
-    if (fused_lds_bytes(ws * hs, c->bitmap_words, false) > (size_t)c->prop.sharedMemPerBlock)
-        return fail(c, PCORE_E_INVALID_ARG, "debug_render_clouds: sampled z-buffer does not fit in LDS");
+    int ws, hs;
+    if (const int vr = check_sampling(c, "debug_render_clouds", p->stride, false, "", false, ws, hs)) return vr;
     if (num_poses == 0) return PCORE_OK;
     HIPC(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1499,17 +1398,7 @@ int pcore_debug_render_clouds(pcore_ctx* c, const float* d_poses, const int32_t*
     if (rc != PCORE_OK) return rc;
     FusedArgs a{};
     fill_fused_args(c, p, a);
-    a.poses = d_poses;
-    a.pose_model = d_pose_model;
-    a.pose_label = d_pose_label;
-    a.num_poses = num_poses;
-    a.cloud_out = (float4*)d_out_xyzw;
-    a.cloud_count = d_out_count;
-    a.cloud_cap = ws * hs;
-    a.tcap = fused_tier_samples(0, a.ws, a.hs, 0, false, c->dinfo);
-    if (const char* e = getenv("PCORE_FUSED_TCAP")) a.tcap = std::min(std::max(atoi(e), 1), a.ws * a.hs);
-    if (a.tcap <= 0) a.tcap = a.ws * a.hs;
-    HIPC(c, launch_render_cloud(a, s));
+    HIPC(c, stage_clouds(c, a, d_poses, d_pose_model, d_pose_label, num_poses, (float4*)d_out_xyzw, d_out_count, s));
     return PCORE_OK;
 }
 
@@ -1571,16 +1460,6 @@ int pcore_get_stats(pcore_ctx* c, pcore_gpu_stats* out, int32_t reset) {
     out->gicp_iterations_run = (int64_t)it[1];
     out->gicp_cycle_exits = (int64_t)it[2];
     if (reset) c->peak_mem_mb = 0.0;
-    return PCORE_OK;
-}
-
-int pcore_debug_gicp_help_stats(pcore_ctx* c, int64_t* out4) {
-    if (!c || !out4) return PCORE_E_INVALID_ARG;
-    HIPC(c, hipSetDevice(c->device));
-    for (int i = 0; i < 4; i++) out4[i] = 0;
-    if (c->icp_ev_used <= 0 || !c->icp_iter_stats_host) return PCORE_OK;
-    HIPC(c, hipEventSynchronize(c->icp_ev[3 * (c->icp_ev_used - 1) + 2]));  // after the last chunk's copy
-    for (int i = 0; i < 4; i++) out4[i] = (int64_t)c->icp_iter_stats_host[4 + i];
     return PCORE_OK;
 }
 

@@ -1,8 +1,7 @@
 // pcore_cov.h -- the GICP covariances of a point segment (fast_gicp's k-NN covariances with PLANE regularisation;
 // DESIGN.md section 5): one wave per round of 64 query points, brute-force k-NN over the segment with candidates
 // staged through a 64-point LDS tile, double mean / covariance in list order, Jacobi (<= 6 thresholded sweeps), PLANE regularisation.
-// Shared by covariance_kernel (pcore_gicp.hip: one wave per segment) and render_cloud_kernel (pcore_kernels.hip: the
-// rendered clouds' covariances in the launch that produced them, its four waves taking the query rounds in turn).
+// Used by covariance_kernel and covariance_cloud_kernel (pcore_gicp.hip: one wave per segment).
 // Bit-identical to the oracle's covariance_one (tests/test_gpu_covariances.py, the GICP parity tests).
 #pragma once
 
@@ -10,10 +9,6 @@
 
 #include <climits>
 #include <type_traits>
-
-#ifndef PCORE_COV_SKIP
-#define PCORE_COV_SKIP 0  // ablation timing builds only: bit 0 skips the PLANE regularisation, bit 1 the k-NN search
-#endif
 
 namespace pcore {
 namespace {
@@ -119,12 +114,7 @@ __device__ __forceinline__ void cov_from_list(const Pts& P, const int (&nb)[KMAX
 #pragma unroll
     for (int e = 0; e < 6; e++) c6[e] = c6[e] / kd;
     double r6[6];
-#if PCORE_COV_SKIP & 1  // ablation timing only (wrong results): no eigen-decomposition / PLANE regularisation
-#pragma unroll
-    for (int e = 0; e < 6; e++) r6[e] = c6[e];
-#else
     plane_regularize(c6, r6);
-#endif
 #pragma unroll
     for (int e = 0; e < 6; e++) out6[e] = r6[e];
 }
@@ -182,13 +172,7 @@ __device__ __forceinline__ void cov_knn_round(const float4* P, int n, int k_arg,
         if (cnt < k) cnt++;
         nan_list = nan_list || d != d;
     };
-#if PCORE_COV_SKIP & 2  // ablation timing only (wrong results): the first k points instead of the k-NN search
-    for (int q = 0; q < KMAX; q++)
-        if (q < k && q < n) { nb[q] = q; cnt = q + 1; }
-    for (int j0 = n; j0 < n; j0 += kCovLanes) {
-#else
     for (int j0 = 0; j0 < n; j0 += kCovLanes) {
-#endif
         wave_lds_sync();  // the previous tile is read
         if (j0 + lane < n) tile[lane] = P[j0 + lane];
         wave_lds_sync();
