@@ -13,9 +13,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpcore.so")
-SOURCES = ["pcore_kernels.hip", "pcore_gicp.hip", "pcore_metrics.hip", "pcore_states.hip", "pcore_icp2d.hip", "pcore_p2p.hip",
-           "pcore_api.hip"]
-HEADERS = ["pcore_internal.h", "pcore_cov.h", "pcore_gicp_math.h", "pcore_icp2d_math.h", "pcore_p2p_math.h", "pcore_dmath.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h", os.path.join("..", "..", "include", "pcore.h")]
+SOURCES = ["pcore_fused.hip", "pcore_render.hip", "pcore_cloud.hip", "pcore_gicp.hip", "pcore_metrics.hip", "pcore_states.hip",
+           "pcore_icp2d.hip", "pcore_p2p.hip", "pcore_api.hip"]
+HEADERS = ["pcore_internal.h", "pcore_cov.h", "pcore_gicp_math.h", "pcore_icp2d_math.h", "pcore_p2p_math.h", "pcore_dmath.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h", "pcore_raster.h", "pcore_fused_probe.h", os.path.join("..", "..", "include", "pcore.h")]
 ARCH = os.environ.get("PCORE_OFFLOAD_ARCH", "gfx950")
 
 
@@ -44,7 +44,8 @@ def kernel_source_digest() -> str:
     import hashlib
 
     h = hashlib.sha256(" ".join(flags()).encode())  # the compile flags too: a profile is of one build
-    for f in ("pcore_kernels.hip", "pcore_internal.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h"):
+    for f in ("pcore_fused.hip", "pcore_raster.h", "pcore_fused_probe.h", "pcore_internal.h", "pcore_gicp_math.h",
+              "pcore_dmath.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h"):
         with open(os.path.join(CSRC, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

@@ -1,6 +1,6 @@
 // pcore_api.hip -- C ABI (include/pcore.h) of the MI355X pose-search core: context, static inputs
 // (mesh dedupe + vertex-ring streams, camera), per-scene observation (label sort + neighbour grids) and dispatch of
-// the kernels in pcore_kernels.hip.  Host code; no hidden allocations on the per-batch path (evaluate /
+// the kernels in the other .hip files.  Host code; no hidden allocations on the per-batch path (evaluate /
 // select), scratch for the parity stages grows monotonically.
 #include "../../include/pcore.h"
 #include "pcore_internal.h"
@@ -266,7 +266,7 @@ void build_grid(const std::vector<float4>& pts, float radius, LabelGrid& g, std:
     std::vector<int> cell_of(pts.size());
     std::vector<int> cnt(ncell + 1, 0);
     for (size_t i = 0; i < pts.size(); i++) {
-        // same float formula as the device query (pcore_kernels.hip, process_points)
+        // same float formula as the device query (pcore_fused.hip, process_points)
         const float fx = (pts[i].x - g.ox) * g.inv_c, fy = (pts[i].y - g.oy) * g.inv_c, fz = (pts[i].z - g.oz) * g.inv_c;
         int ix = (int)std::floor(std::max(fx, 0.0f)), iy = (int)std::floor(std::max(fy, 0.0f)),
             iz = (int)std::floor(std::max(fz, 0.0f));

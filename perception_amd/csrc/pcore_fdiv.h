@@ -76,7 +76,7 @@ __device__ __forceinline__ bool absbits_range_ok(uint32_t umin, uint32_t umax) {
     return umin >= (87u << 23) && umax < (168u << 23);
 }
 
-// The fragment test's barycentrics without the reference's three halves (fragment<true>, pcore_kernels.hip).  The
+// The fragment test's barycentrics without the reference's three halves (fragment<true>, pcore_raster.h).  The
 // reference computes area = 0.5 Y, beta = (0.5 X) * (1 / area) with Y and X the rounded cross products of coordinate
 // differences.  Scaling a float by 0.5 or 2 is exact unless the result is denormal or overflows, and commutes with a
 // correctly rounded division under the same condition, so

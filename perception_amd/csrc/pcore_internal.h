@@ -1,5 +1,5 @@
 // pcore_internal.h -- data layouts shared by the host API (pcore_api.hip) and the kernels
-// (pcore_kernels.hip).  Not part of the ABI.
+// (pcore_fused.hip, pcore_render.hip, pcore_cloud.hip, pcore_gicp.hip, ...).  Not part of the ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,7 +24,7 @@ namespace pcore {
 // All loads of a step are unconditional (the next step's triangle slots and the next unconsumed vertex pass
 // are prefetched while the current step runs), so the compiler counts them in vmcnt.
 constexpr int kStepSlots = 64;
-// Per-vertex sample-window bounds (packed int16, computed once per vertex in the vertex pass; pcore_kernels.hip,
+// Per-vertex sample-window bounds (packed int16, computed once per vertex in the vertex pass; pcore_fused.hip,
 // vertex_bounds).  A batch reads the bounds of the last kRefPasses passes only, so they live in two ring buffers of
 // their own: pass p in buffer p mod 2, which equals (p mod kVRing) mod 2 because kVRing is even.
 #ifndef PCORE_VRING
@@ -56,7 +56,7 @@ struct LabelGrid {
 // tile tiers of the fused window launch: workgroups per CU PCORE_TIER_MAX, ..., 3, 2 (the LDS tile that
 // leaves room for that many workgroups); the host picks the tier from the previous call's window histogram
 #ifndef PCORE_DEBUG_SKIP_RT
-#define PCORE_DEBUG_SKIP_RT 0  // 1: the fused kernels honour PCORE_DEBUG_SKIP (ablation builds, tools/ablate_sq.sh)
+#define PCORE_DEBUG_SKIP_RT 0  // 1: the fused kernels honour PCORE_DEBUG_SKIP (pcore_fused_probe.h, tools/ablate_sq.sh)
 #endif
 #ifndef PCORE_TIER_MAX
 #define PCORE_TIER_MAX 6
@@ -133,7 +133,7 @@ struct FusedArgs {
     int32_t sel_models;
 };
 
-// GICP over a chunk of poses (pcore_kernels.hip, gicp_kernel)
+// GICP over a chunk of poses (pcore_gicp.hip, gicp_kernel)
 struct GicpArgs {
     const float4* src;        // chunk-local per-pose slots: src + pose * src_cap
     const int32_t* src_count;
@@ -213,7 +213,9 @@ struct DeviceInfo {
 // resident gicp_kernel workgroups per CU (occupancy query of the persistent launch)
 hipError_t gicp_occupancy_per_cu(int* per_cu);
 
-// launchers (pcore_kernels.hip)
+// launchers; each is defined in the file of its kernel (pcore_fused.hip: render_cloud, fused_cost, window_probe;
+// pcore_gicp.hip: covariances, gicp; pcore_render.hip: render_full, render_finalize, fill_i32; pcore_cloud.hip: cloud_*,
+// exclusive_scan, sample_source, select)
 hipError_t launch_render_cloud(const FusedArgs& a, hipStream_t s);
 // brute-force k-NN covariances, one workgroup per segment; segments above max_n points are skipped
 hipError_t launch_covariances(const float4* pts, const int32_t* seg_off, const int32_t* seg_cnt, int seg_stride,

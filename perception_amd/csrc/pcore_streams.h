@@ -384,10 +384,7 @@ inline void build_model_order(const std::vector<int>& tv, const std::vector<floa
 // look-ahead batches (kAhead) and the band orders (three axes, a few band counts) are candidates.  A candidate is
 // eligible when it needs no more passes and no more steps than the baseline, so no mesh ever gets more of either;
 // among the eligible ones the cheapest wins, a vertex pass weighing two steps (about 62 against 30 vector instructions
-// per wave in the fused kernel), the earliest on a tie.  -DPCORE_STREAM_CANDIDATES=0 keeps the baseline (A/B).
-#ifndef PCORE_STREAM_CANDIDATES
-#define PCORE_STREAM_CANDIDATES 1
-#endif
+// per wave in the fused kernel), the earliest on a tie.
 inline void build_model(const std::vector<int>& tv, const std::vector<float>& vxyz, int tri_base, int num_streams,
                         int vring, int ref_passes, Built& out, int chunks = 4) {
     if (tv.empty()) return;
@@ -396,7 +393,6 @@ inline void build_model(const std::vector<int>& tv, const std::vector<float>& vx
     build_model_order(tv, vxyz, grow, tri_base, num_streams, vring, ref_passes, w, chunks);
     build_model_order(tv, vxyz, sweep, tri_base, num_streams, vring, ref_passes, b, chunks);
     if (b.passes < w.passes || (b.passes == w.passes && b.steps < w.steps)) std::swap(w, b);
-#if PCORE_STREAM_CANDIDATES
     const long long base_passes = w.passes, base_steps = w.steps;
     auto offer = [&](const std::vector<int>& order) {
         Built c;
@@ -408,7 +404,6 @@ inline void build_model(const std::vector<int>& tv, const std::vector<float>& vx
     offer(sweep);
     for (int axis = 0; axis < 3; axis++)
         for (int bands : {1, 2, 3, 4, 6, 8}) offer(band_order(tv, vxyz, axis, bands));
-#endif
     const int step0 = (int)(out.stris.size() / 64), pass0 = (int)(out.sverts.size() / 64);
     out.sverts.insert(out.sverts.end(), w.sverts.begin(), w.sverts.end());
     out.stris.insert(out.stris.end(), w.stris.begin(), w.stris.end());

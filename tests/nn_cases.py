@@ -8,7 +8,7 @@ grid, in a grid whose cell is set by the extent of a segment with a far point --
 depth image.  tests/test_nn_cases.py certifies on the CPU that each case can tell a wrong search from a right one;
 tests/test_gpu_nn_adversarial.py runs them through the C ABI, bit for bit against the oracle's brute force.
 
-The neighbour grid (build_grid, pcore_api.hip) and the radius box of the query (process_points, pcore_kernels.hip) are
+The neighbour grid (build_grid, pcore_api.hip) and the radius box of the query (process_points, pcore_fused.hip) are
 restated here in float32 numpy with the same formulas, because the placements depend on where the float cell faces lie.
 """
 from __future__ import annotations
@@ -115,7 +115,7 @@ def parent_pad(r):
     return np.sqrt(r2_of(r)) * F32(1.0001) + F32(1e-7)
 
 
-BOX_ROUND = F32(1.0e-6)  # kBoxRound of pcore_kernels.hip: cells of slack per cell of the grid's longest axis
+BOX_ROUND = F32(1.0e-6)  # kBoxRound of pcore_fused.hip: cells of slack per cell of the grid's longest axis
 
 
 def box_of(g, q, r, parent=False):
