@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define PCORE_ABI_VERSION 8
+#define PCORE_ABI_VERSION 9
 
 enum pcore_status {
     PCORE_OK = 0,
@@ -218,6 +218,16 @@ int pcore_icp_planar(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose
  * DESIGN.md section 5) of n records of 10 doubles -- n, sum qx, sum qy, sum tx, sum ty, sum qx tx, sum qx ty,
  * sum qy tx, sum qy ty, sum d^2 -- into d_out (n x 4: c', s', tx', ty'), one thread each. */
 int pcore_debug_planar_step(const double* d_sums, double* d_out, int32_t n, pcore_stream stream);
+
+/* Test hook (no reference counterpart): the colour gate's CIEDE2000 distance (compute_costs.cuh:90-158) as the fused
+ * cost kernel of cost_type 1 evaluates it on the device: n pairs of six floats (l1 a1 b1 l2 a2 b2) into d_out (n
+ * doubles), one thread each. */
+int pcore_debug_colour_distance(const float* d_lab_pairs, double* d_out, int32_t n, pcore_stream stream);
+
+/* Test hook (no reference counterpart): the RGB -> Lab conversion that pcore_upload_meshes and
+ * pcore_set_observation_colors store, of n colours (3 bytes each, in the order they are given there) into out_lab
+ * (n x 3 floats: L a b).  Host only: both pointers are host memory and no device is needed. */
+int pcore_debug_rgb2lab(const uint8_t* rgb, float* out_lab, int32_t n);
 
 /* Point-to-plane ICP against a projective scene (cuda_icp: ICP_Point2Plane_cuda, icp.cu:157-218; Scene_projective,
  * depth_scene.h; get_normal, scene/common.cpp:17-107).  A correspondence is one projection and one gather from the

@@ -420,6 +420,9 @@ def _colour_lib():
         L.orc_rgb2lab.argtypes = [_u8p, _f32p]
         L.orc_colour_distance.argtypes = [_f32p, _f32p]
         L.orc_colour_distance.restype = ctypes.c_double
+        L.orc_rgb2lab_n.argtypes = [_u8p, ctypes.c_int, _f32p]
+        L.orc_colour_distance_n.argtypes = [_f32p, ctypes.c_int,
+                                            np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")]
         for n in ("orc_sin_f", "orc_cos_f", "orc_exp_f"):
             getattr(L, n).argtypes = [f]
             getattr(L, n).restype = f
@@ -442,6 +445,24 @@ def rgb2lab(rgb):
 
 def colour_distance(lab1, lab2) -> float:
     return _colour_lib().orc_colour_distance(_c(lab1, np.float32).reshape(3), _c(lab2, np.float32).reshape(3))
+
+
+def rgb2lab_n(rgb) -> np.ndarray:
+    """(n, 3) uint8 -> (n, 3) float32: rgb2lab of every row."""
+    rgb = _c(rgb, np.uint8).reshape(-1, 3)
+    out = np.zeros((len(rgb), 3), np.float32)
+    if len(rgb):
+        _colour_lib().orc_rgb2lab_n(rgb.reshape(-1), len(rgb), out.reshape(-1))
+    return out
+
+
+def colour_distance_n(lab_pairs) -> np.ndarray:
+    """(n, 6) float32 (l1 a1 b1 l2 a2 b2) -> (n,) float64: colour_distance of every row."""
+    p = _c(lab_pairs, np.float32).reshape(-1, 6)
+    out = np.zeros(len(p), np.float64)
+    if len(p):
+        _colour_lib().orc_colour_distance_n(p.reshape(-1), len(p), out)
+    return out
 
 
 def colour_math(name, *args) -> float:

@@ -1138,6 +1138,16 @@ double orc_colour_distance(const float* lab1, const float* lab2) {
     return pcore::colour::colour_distance(lab1[0], lab1[1], lab1[2], lab2[0], lab2[1], lab2[2]);
 }
 
+// the two above over arrays: n colours (3 bytes each) -> n x 3 floats; n pairs of six floats -> n doubles
+void orc_rgb2lab_n(const uint8_t* rgb, int n, float* out_lab) {
+    for (int i = 0; i < n; i++) orc_rgb2lab(rgb + (size_t)3 * i, out_lab + (size_t)3 * i);
+}
+
+void orc_colour_distance_n(const float* lab_pairs, int n, double* out) {
+#pragma omp parallel for schedule(static)
+    for (int i = 0; i < n; i++) out[i] = orc_colour_distance(lab_pairs + (size_t)6 * i, lab_pairs + (size_t)6 * i + 3);
+}
+
 float orc_sin_f(float x) { return pcore::colour::sin_f(x); }
 float orc_cos_f(float x) { return pcore::colour::cos_f(x); }
 float orc_exp_f(float x) { return pcore::colour::exp_f(x); }

@@ -170,6 +170,8 @@ void orc_evaluate_icp(const float* tris, int num_tris, const int32_t* tris_model
  * the first triangle that reaches each pixel's minimum depth). */
 void orc_rgb2lab(const uint8_t c[3], float lab[3]);
 double orc_colour_distance(const float* lab1, const float* lab2);
+void orc_rgb2lab_n(const uint8_t* rgb, int n, float* out_lab);
+void orc_colour_distance_n(const float* lab_pairs, int n, double* out);
 float orc_sin_f(float x);
 float orc_cos_f(float x);
 float orc_exp_f(float x);

@@ -33,10 +33,10 @@ EXPORTED_SYMBOLS = (
     "pcore_count_within", "pcore_state_poses", "pcore_evaluate_select", "pcore_get_tile_info", "pcore_debug_lm_solve",
     "pcore_debug_covariances", "pcore_debug_covariances_cloud", "pcore_depth_to_cloud_ex",
     "pcore_icp_planar", "pcore_debug_planar_step",
-    "pcore_scene_projective", "pcore_debug_render_clouds",
+    "pcore_scene_projective", "pcore_debug_render_clouds", "pcore_debug_colour_distance",
 )
 # declared in include/pcore.h too; kept apart because tests/test_abi.py's symbol pattern stops at a digit
-EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds")
+EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds", "pcore_debug_rgb2lab")
 
 
 class PcoreError(RuntimeError):
@@ -186,6 +186,9 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                              ctypes.POINTER(P2pIcpParams), vp, vp, vp, vp, vp]
     if hasattr(L, "pcore_debug_render_clouds"):  # absent from older A/B builds (PCORE_LIB)
         L.pcore_debug_render_clouds.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(EvalParams), vp, vp, vp]
+    if hasattr(L, "pcore_debug_colour_distance"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_debug_colour_distance.argtypes = [vp, vp, i32, vp]
+        L.pcore_debug_rgb2lab.argtypes = [vp, vp, i32]
     L.pcore_select.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp]
     L.pcore_pose_distances.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.pcore_set_observation_colors.argtypes = [vp, vp, i32, vp]

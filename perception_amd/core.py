@@ -280,6 +280,30 @@ class PoseCore:
             raise PcoreError(rc, "pcore_debug_planar_step failed")
         return out
 
+    def colour_distance(self, lab_pairs: torch.Tensor, stream=None) -> torch.Tensor:
+        """pcore_debug_colour_distance (test hook): the colour gate's CIEDE2000 distance of (n, 6) float32 Lab pairs
+        (l1 a1 b1 l2 a2 b2) as the fused cost kernel evaluates it -> (n,) float64."""
+        lab_pairs = lab_pairs.contiguous()
+        n = int(lab_pairs.shape[0])
+        out = torch.empty(n, dtype=torch.float64, device=lab_pairs.device)
+        rc = self.lib.pcore_debug_colour_distance(_ptr(lab_pairs, torch.float32, "lab_pairs"),
+                                                  _ptr(out, torch.float64, "out"), n, _stream(stream))
+        if rc != _native.PCORE_OK:
+            raise PcoreError(rc, "pcore_debug_colour_distance failed")
+        return out
+
+    @staticmethod
+    def rgb2lab(rgb: np.ndarray) -> np.ndarray:
+        """pcore_debug_rgb2lab (test hook, host only, no context): the Lab values upload_meshes and
+        set_observation_colors store for (n, 3) uint8 colours -> (n, 3) float32."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        out = np.empty((rgb.shape[0], 3), np.float32)
+        rc = _native.load().pcore_debug_rgb2lab(rgb.ctypes.data_as(ctypes.c_void_p),
+                                                out.ctypes.data_as(ctypes.c_void_p), rgb.shape[0])
+        if rc != _native.PCORE_OK:
+            raise PcoreError(rc, "pcore_debug_rgb2lab failed")
+        return out
+
     def scene_projective(self, depth_cm: torch.Tensor, fx: float, fy: float, cx: float, cy: float, stream=None
                          ) -> Tuple[torch.Tensor, torch.Tensor]:
         """pcore_scene_projective: the reference's Scene_projective buffers of an (H, W) int32 cm depth image ->

@@ -1489,6 +1489,23 @@ int pcore_debug_lm_solve(const double* d_sys, const double* d_lambda, double* d_
     return launch_lm_solve_test(d_sys, d_lambda, d_out, n, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
 }
 
+int pcore_debug_colour_distance(const float* d_lab_pairs, double* d_out, int32_t n, pcore_stream stream) {
+    if (n < 0 || (n > 0 && (!d_lab_pairs || !d_out))) return PCORE_E_INVALID_ARG;
+    return launch_colour_distance_test(d_lab_pairs, d_out, n, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
+}
+
+// Test hook: lab_of, the conversion pcore_upload_meshes and pcore_set_observation_colors store (host only).
+int pcore_debug_rgb2lab(const uint8_t* rgb, float* out_lab, int32_t n) {
+    if (n < 0 || (n > 0 && (!rgb || !out_lab))) return PCORE_E_INVALID_ARG;
+    for (int32_t i = 0; i < n; i++) {
+        const float4 v = lab_of(rgb + 3 * (size_t)i);
+        out_lab[3 * (size_t)i] = v.x;
+        out_lab[3 * (size_t)i + 1] = v.y;
+        out_lab[3 * (size_t)i + 2] = v.z;
+    }
+    return PCORE_OK;
+}
+
 int pcore_debug_covariances(const float* d_xyzw, const int32_t* d_seg_off, const int32_t* d_seg_cnt, int32_t num_segs,
                             int32_t k, double* d_out_cov6, pcore_stream stream) {
     if (num_segs < 0 || k <= 0 || k > 16 || (num_segs > 0 && (!d_xyzw || !d_seg_off || !d_seg_cnt || !d_out_cov6)))

@@ -1053,4 +1053,21 @@ hipError_t launch_fused_cost(const FusedArgs& a0, hipStream_t s) {
     return hipGetLastError();
 }
 
+// Test hook of the colour gate's distance (pcore_debug_colour_distance): colour::colour_distance of n pairs of six
+// floats (l1 a1 b1 l2 a2 b2), one thread each, called as process_points calls it on (observed, rendered).
+__global__ void __launch_bounds__(256) colour_distance_test_kernel(const float* lab_pairs, double* out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* p = lab_pairs + (size_t)6 * i;
+    const float4 lo = make_float4(p[0], p[1], p[2], 0.0f), lr = make_float4(p[3], p[4], p[5], 0.0f);
+    const double cd = colour::colour_distance(lo.x, lo.y, lo.z, lr.x, lr.y, lr.z);
+    out[i] = cd;
+}
+
+hipError_t launch_colour_distance_test(const float* lab_pairs, double* out, int n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(colour_distance_test_kernel, dim3((n + 255) / 256), dim3(256), 0, s, lab_pairs, out, n);
+    return hipGetLastError();
+}
+
 }  // namespace pcore

@@ -8,11 +8,16 @@ grid, in a grid whose cell is set by the extent of a segment with a far point --
 depth image.  tests/test_nn_cases.py certifies on the CPU that each case can tell a wrong search from a right one;
 tests/test_gpu_nn_adversarial.py runs them through the C ABI, bit for bit against the oracle's brute force.
 
+The colour family at the end gives three of these geometries a colour per triangle and per observed point (cost type 1:
+which triangle colours a sample, and on which side of the CIEDE2000 gate the pair falls, then decide the costs);
+tests/test_gpu_colour.py runs it.
+
 The neighbour grid (build_grid, pcore_api.hip) and the radius box of the query (process_points, pcore_fused.hip) are
 restated here in float32 numpy with the same formulas, because the placements depend on where the float cell faces lie.
 """
 from __future__ import annotations
 
+import copy
 import functools
 from types import SimpleNamespace
 
@@ -264,13 +269,13 @@ class NNCase:
         return self.obs_sorted[a:b], np.arange(a, b)
 
     # -- the oracle's side ------------------------------------------------------------------------
-    def oracle_costs(self, cost_type, calc_obs=True):
+    def oracle_costs(self, cost_type, calc_obs=True, colour_thr=COLOUR_THR):
         c = self.cam
         if cost_type == 1:
             return oracle.evaluate_colour(self.bank.tris, self.bank.colors, self.bank.tris_model_count, self.poses,
                                           self.pose_model, self.width, self.height, self.proj, self.src_depth, 1.0,
                                           self.stride, c["cx"], c["cy"], c["fx"], c["fy"], 100.0, self.obs_sorted,
-                                          self.rgb_sorted, self.pose_obs_total0, calc_obs, self.r, COLOUR_THR)
+                                          self.rgb_sorted, self.pose_obs_total0, calc_obs, self.r, colour_thr)
         six = cost_type == 2
         return oracle.evaluate(self.bank.tris, self.bank.tris_model_count, self.poses, self.pose_model,
                                self.pose_label if six else None, self.width, self.height, self.proj, self.src_depth,
@@ -643,6 +648,208 @@ def segments_case(r=0.01):
     pts = np.concatenate(pts).astype(F32)
     case.set_observation(pts, labs, _rgb_for(labs, rng.random(len(pts)) < 0.5), seed=29)
     return case
+
+
+# ---------------------------------------------------------------------------------------------
+# family: per-triangle colours (cost type 1: the fused kernel's colour id pass and the CIEDE2000 gate)
+# ---------------------------------------------------------------------------------------------
+
+COLOUR_BASE = np.array((120, 130, 110))  # every triangle and every observed point: the base + U[-40, 40] per channel,
+COLOUR_SPREAD = 40                       # which puts about a third of the random pairs within the gate at 15
+COLOUR_GEOMETRIES = ("segments-s4", "segments-s5", "ties-TINY-s1")
+COLOUR_VARIANTS = ("plain", "dup", "rev")
+DUP_PER_MODEL = 48
+
+
+@functools.lru_cache(maxsize=None)
+def _colour_geometry(geom):
+    """The camera, stride, poses and observed points of a colour case: the `segments` case at stride 4, the same
+    observation seen at stride 5, and the r = 0.003 tie case (TINY, stride 1).  Built once; no colour case changes it."""
+    if geom == "segments-s4":
+        return _cover_poses(segments_case())
+    if geom == "segments-s5":
+        b = _colour_geometry("segments-s4")
+        c = NNCase("segments-s5", b.cam, 5, b.r, b.poses44, b.pose_model, b.pose_label)
+        c.obs_xyz, c.obs_label, c.obs_rgb = b.obs_xyz, b.obs_label, b.obs_rgb
+        c.finish()
+        return _cover_poses(c)
+    assert geom == "ties-TINY-s1"
+    return _cover_poses(tie_case(0.003))
+
+
+MIN_GATED = 60
+
+
+def _cover_poses(case):
+    """The observations of the depth cases leave some poses (the second plane, the tilted ones, the poses of the small
+    segments) with few or no rendered points within r of an observed point, and a pose without gated pairs cannot show
+    a wrong colour.  Every pose with fewer than MIN_GATED such points gets, appended to the observation with label -1,
+    an observed point 0.4 r beside every second rendered point of its own."""
+    d2, idx = oracle.knn1(case.Q, None, case.obs_sorted)
+    gated = np.bincount(case.q_pose[(d2 <= r2_of(case.r)) & (idx >= 0)], minlength=case.n)
+    num = np.bincount(case.q_pose, minlength=case.n)
+    add = [case.Q[case.q_pose == p][::2] + np.array([0.4 * case.r, 0, 0], F32)
+           for p in np.nonzero((gated < MIN_GATED) & (num > 0))[0]]
+    if add:
+        add = np.concatenate(add).astype(F32)
+        case.obs_xyz = np.ascontiguousarray(np.concatenate([case.obs_xyz, add]))
+        case.obs_label = np.ascontiguousarray(np.concatenate([case.obs_label, np.full(len(add), -1, np.int32)]))
+        case.obs_rgb = np.ascontiguousarray(np.concatenate([case.obs_rgb, np.zeros((len(add), 3), np.uint8)]))
+        case.finish()
+    return case
+
+
+def _random_rgb(rng, n):
+    return (COLOUR_BASE[None, :] + rng.integers(-COLOUR_SPREAD, COLOUR_SPREAD + 1, (n, 3))).astype(np.uint8)
+
+
+def _with_mesh(base, name, tris, colors, obs_rgb):
+    """A shallow copy of the geometry with other meshes (a list of (tris, colours) per model) and observed colours."""
+    case = copy.copy(base)
+    case.name, case.meta = name, {}
+    case.bank = _bank()
+    for m, t, c in zip(case.bank.models, tris, colors):
+        m.tris = np.ascontiguousarray(t, F32).reshape(-1, 9)
+        m.colors = np.ascontiguousarray(c, np.uint8).reshape(-1, 3)
+    case.obs_rgb = np.ascontiguousarray(obs_rgb, np.uint8)
+    case.finish()
+    return case
+
+
+def sample_triangles(case):
+    """The triangle (index into the concatenated mesh) whose colour each rendered point of case.Q has: the oracle's
+    colour planes of the mesh with every triangle's index written into its three colour bytes."""
+    T = len(case.bank.tris)
+    i = np.arange(T)
+    code = np.stack([i & 255, (i >> 8) & 255, i >> 16], 1).astype(np.uint8)
+    z, col = oracle.render_depth_color(case.bank.tris, code, case.bank.tris_model_count, case.poses, case.pose_model,
+                                       None, case.width, case.height, case.proj, case.src_depth, None, 1.0)
+    s = case.stride
+    assert np.array_equal(z[:, ::s, ::s][case.q_pose, case.q_ky, case.q_kx], case.q_Z)
+    b = col[:, :, ::s, ::s][:, case.q_pose, case.q_ky, case.q_kx].astype(np.int64)
+    tid = b[0] | (b[1] << 8) | (b[2] << 16)
+    hi = np.cumsum(case.bank.tris_model_count)
+    lo = hi - case.bank.tris_model_count
+    m = case.pose_model[case.q_pose]
+    assert ((tid >= lo[m]) & (tid < hi[m])).all()  # a rendered point has a triangle of its pose's model
+    return tid
+
+
+def gated_pairs(case, nn=None):
+    """The (observed point, triangle) pairs whose colour distance the cost of type 1 tests: the rendered points with a
+    nearest observed point within r.  Returns a namespace of arrays over the pairs: q (index into case.Q), pose, obs
+    (position in the label-sorted cloud), tri, d (the oracle's colour distance); and bad_r (n,), the rendered points
+    per pose without a neighbour within r.  nn: (d2, index) of each rendered point's nearest observed point of the
+    whole cloud (the oracle's brute force when None)."""
+    d2, idx = oracle.knn1(case.Q, None, case.obs_sorted) if nn is None else nn
+    tid = sample_triangles(case)
+    near = d2 <= r2_of(case.r)
+    q = np.nonzero(near & (idx >= 0))[0]
+    lab_o = oracle.rgb2lab_n(case.rgb_sorted)
+    lab_t = oracle.rgb2lab_n(case.bank.colors)
+    d = oracle.colour_distance_n(np.concatenate([lab_o[idx[q]], lab_t[tid[q]]], 1))
+    return SimpleNamespace(q=q, pose=case.q_pose[q], obs=idx[q].astype(np.int64), tri=tid[q], d=d,
+                           bad_r=np.bincount(case.q_pose[~near], minlength=case.n),
+                           num=np.bincount(case.q_pose, minlength=case.n))
+
+
+def colour_costs_np(case, pairs, thr, calc_obs=True):
+    """The costs of type 1 from the gated pairs, in the reference's float order: a pair beyond the threshold is bad, a
+    pair within it marks its observed point explained."""
+    within = ~(pairs.d > np.float64(F32(thr)))
+    rc, oc, df = (np.zeros(case.n, F32) for _ in range(3))
+    for p in range(case.n):
+        mine = pairs.pose == p
+        num = F32(pairs.num[p])
+        nbad = F32(pairs.bad_r[p] + (mine & ~within).sum())
+        expl = F32(len(np.unique(pairs.obs[mine & within])))
+        r = F32(-1.0) if num == 0 else nbad / num
+        rc[p] = r if r == F32(-1.0) else r * F32(100.0)
+        if calc_obs:
+            tot = case.pose_obs_total0[p]
+            df[p] = (num - nbad) - expl
+            oc[p] = (tot - expl) / tot * F32(100.0)
+    return rc, oc, df
+
+
+def _other_side(rng, rgb_o, d, thr):
+    """A colour whose distance to the observed colour rgb_o is on the other side of thr than d: the observed colour
+    itself (distance 0) for a pair beyond the gate, a random colour beyond the gate for a pair within it."""
+    if d > thr:
+        return rgb_o.copy()
+    lab_o = oracle.rgb2lab(rgb_o)
+    for _ in range(200):
+        c = rng.integers(0, 256, 3).astype(np.uint8)
+        if oracle.colour_distance(lab_o, oracle.rgb2lab(c)) > thr:
+            return c
+    raise AssertionError("no colour beyond the gate")
+
+
+@functools.lru_cache(maxsize=None)
+def colour_case(geom, variant="plain"):
+    """plain: every triangle and every observed point with a random colour of its own.  dup: DUP_PER_MODEL triangles
+    per model that colour gated samples are appended to their model once more, each copy with a colour on the other
+    side of the gate (from its original, against the observed point of the original's first gated pair): the original,
+    with the lower index, has to win every sample.  dup-front: the same copies BEFORE the originals (the certificate's
+    counter-example: there the copies win).  rev: the plain mesh with the triangles, and their colours, in reverse
+    order within each model: the same depths, the other winner wherever two triangles tie in depth."""
+    base = _colour_geometry(geom)
+    seed = 101 + COLOUR_GEOMETRIES.index(geom.replace("s5", "s4"))  # both strides of `segments`: the same mesh colours
+    rng = np.random.default_rng(seed)
+    cnt = base.bank.tris_model_count
+    tris = [m.tris for m in base.bank.models]
+    cols = np.split(_random_rgb(rng, int(cnt.sum())), np.cumsum(cnt)[:-1])
+    obs_rgb = _random_rgb(rng, len(base.obs_xyz))
+    name = f"colour-{geom}-{variant}"
+    if variant == "plain":
+        return _with_mesh(base, name, tris, cols, obs_rgb)
+    if variant == "rev":
+        return _with_mesh(base, name, [t[::-1] for t in tris], [c[::-1] for c in cols], obs_rgb)
+    assert variant in ("dup", "dup-front")
+    plain = colour_case(geom, "plain")
+    pairs = gated_pairs(plain)
+    lo = np.concatenate([[0], np.cumsum(cnt)[:-1]])
+    dt, dc, chosen = [], [], []
+    for m in range(len(cnt)):
+        ids = np.unique(pairs.tri[(pairs.tri >= lo[m]) & (pairs.tri < lo[m] + cnt[m])])
+        assert len(ids) >= DUP_PER_MODEL, (m, len(ids))
+        ids = ids[np.linspace(0, len(ids) - 1, DUP_PER_MODEL).astype(int)]
+        first = [np.nonzero(pairs.tri == t)[0][0] for t in ids]
+        dt.append(tris[m][ids - lo[m]])
+        dc.append(np.stack([_other_side(rng, plain.rgb_sorted[pairs.obs[k]], pairs.d[k], COLOUR_THR) for k in first]))
+        chosen.append(ids)
+    if variant == "dup":
+        case = _with_mesh(base, name, [np.concatenate([t, d]) for t, d in zip(tris, dt)],
+                          [np.concatenate([c, d]) for c, d in zip(cols, dc)], obs_rgb)
+    else:
+        case = _with_mesh(base, name, [np.concatenate([d, t]) for t, d in zip(tris, dt)],
+                          [np.concatenate([d, c]) for c, d in zip(cols, dc)], obs_rgb)
+    case.meta["copied"] = chosen
+    return case
+
+
+def queued_records(case, pose):
+    """How many (triangle, sample) records raster_phase queues for a pose: over the model's triangles whose sample
+    window (the reference's bounding box and loop bounds, restated in float64) holds 1 to kSmallK = 4 samples, the
+    samples.  The triangles go to the workgroup's 4 waves by stream, and a wave's ring holds kRecCap = 128 records."""
+    m = int(case.pose_model[pose])
+    P = case.poses[pose].astype(np.float64).reshape(4, 4)
+    v = case.bank.models[m].tris.astype(np.float64).reshape(-1, 3)
+    cam = v @ P[:3, :3].T + P[:3, 3]
+    pj = case.proj.astype(np.float64).reshape(4, 4)
+    W, H, s = case.width, case.height, case.stride
+    with np.errstate(all="ignore"):
+        sx = ((np.c_[cam, np.ones(len(cam))] @ pj[0]) / cam[:, 2] * W / 2 + W / 2).reshape(-1, 3)
+        sy = ((np.c_[cam, np.ones(len(cam))] @ pj[1]) / cam[:, 2] * H / 2 + H / 2).reshape(-1, 3)
+    x0 = np.trunc(np.maximum(0, sx.min(1)) + 0.5)
+    x1 = np.floor(np.minimum(W - 1, sx.max(1)))
+    y0 = np.trunc(np.maximum(0, sy.min(1)) + 0.5)
+    y1 = np.floor(np.minimum(H - 1, sy.max(1)))
+    nx = np.floor(x1 / s) - np.ceil(x0 / s) + 1
+    ny = np.floor((H - 1 - y0) / s) - np.ceil((H - 1 - y1) / s) + 1
+    nk = np.where((nx > 0) & (ny > 0), nx * ny, 0)
+    small = (nk >= 1) & (nk <= 4)
+    return int(small.sum()), int(nk[small].sum())
 
 
 # ---------------------------------------------------------------------------------------------

@@ -64,6 +64,41 @@ def test_rgb2lab_matches_python_double():
         assert np.allclose(oracle.rgb2lab(c), _rgb2lab_py(c), rtol=0, atol=2e-5)
 
 
+def test_library_rgb2lab_equals_the_oracle_bitwise():
+    """pcore_debug_rgb2lab -- the conversion pcore_upload_meshes and pcore_set_observation_colors store, a second
+    definition of the oracle's rgb2lab -- on the lattice of channel values 0, 16, ..., 240, 255, every grey, the
+    channel values 10 and 11 either side of the sRGB switch at 0.04045 in every channel (with neighbours and extremes
+    in the others), every colour with all channels <= 40 (the cube root / linear switch at 0.008856 of X, Y and Z is
+    crossed inside it) and 20,000 random colours.  Host code: needs the library, no device."""
+    from perception_amd.core import PoseCore
+
+    lat = np.array(list(range(0, 256, 16)) + [255])
+    low = np.array([0, 9, 10, 11, 12, 128, 255])
+    sets = [np.stack(np.meshgrid(lat, lat, lat, indexing="ij"), -1).reshape(-1, 3),
+            np.repeat(np.arange(256)[:, None], 3, 1),
+            np.stack(np.meshgrid(low, low, low, indexing="ij"), -1).reshape(-1, 3),
+            np.stack(np.meshgrid(*[np.arange(41)] * 3, indexing="ij"), -1).reshape(-1, 3),
+            np.random.default_rng(5).integers(0, 256, (20000, 3))]
+    assert len(sets[0]) == 17 ** 3
+    rgb = np.concatenate(sets).astype(np.uint8)
+    # both sides of both switches are there, in every channel (the cost's channel order: c[2] is red)
+    v = rgb[:, ::-1] / 255.0
+    assert ((v > 0.04045).sum(0) > 10).all() and ((v <= 0.04045).sum(0) > 10).all()
+    assert all(((rgb[:, k] == 10) | (rgb[:, k] == 11)).sum() > 10 for k in range(3))
+    lin = np.where(v > 0.04045, ((v + 0.055) / 1.055) ** 2.4, v / 12.92) * 100.0
+    M = np.array([[0.4124564, 0.3575761, 0.1804375], [0.2126729, 0.7151522, 0.0721750],
+                  [0.0193339, 0.1191920, 0.9503041]])
+    xyz = lin @ M.T / np.array([95.047, 100.0, 108.883])
+    assert ((xyz > 0.008856).sum(0) > 10).all() and ((xyz <= 0.008856).sum(0) > 10).all()
+    dark = rgb[(rgb <= 40).all(1)]
+    xd = xyz[(rgb <= 40).all(1)]
+    assert len(dark) >= 41 ** 3 and ((xd > 0.008856).sum(0) > 10).all() and ((xd <= 0.008856).sum(0) > 10).all()
+    got, want = PoseCore.rgb2lab(rgb), oracle.rgb2lab_n(rgb)
+    assert np.array_equal(want[:5], np.stack([oracle.rgb2lab(c) for c in rgb[:5]]))  # the batched entry is the scalar one
+    bad = np.nonzero((got.view(np.uint32) != want.view(np.uint32)).any(1))[0]
+    assert len(bad) == 0, (len(bad), rgb[bad[:5]], got[bad[:5]], want[bad[:5]])
+
+
 def _ciede_ref_double(l1, a1, b1, l2, a2, b2):
     """compute_costs.cuh:90-158 evaluated in float64 throughout (no float rounding)."""
     pi = math.pi

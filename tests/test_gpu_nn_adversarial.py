@@ -58,11 +58,11 @@ def _want(name, cost_type):
     return _ORACLE[name, cost_type]
 
 
-def _evaluate(core, t, case, cost_type, **kw):
+def _evaluate(core, t, case, cost_type, colour_thr=nc.COLOUR_THR, **kw):
     six = cost_type == 2
     return core.evaluate(t["poses"], t["pm"], t["pl"] if six else None, t["tot"] if six else t["tot0"],
                          cost_type=cost_type, stride=case.stride, sensor_resolution=case.r,
-                         color_distance_threshold=nc.COLOUR_THR, **kw)
+                         color_distance_threshold=colour_thr, **kw)
 
 
 @pytest.fixture(scope="module", params=nc.CASE_NAMES)

@@ -15,6 +15,11 @@ exactly r, a tie, a neighbour across a cell face) are asserted on the oracle's n
   candidates from the first x cell only    faces-*
   the box without its rounding bound       stretched-r0.0075-far-30-axis0, -far-60-axis0, -far-30-axis1, -far-60-axis1,
                                            stretched-r0.003-far-30-axis0
+
+The colour cases (cost type 1, a colour per triangle) are certified at the end, from the oracle alone:
+  a colour table rolled by one triangle    colour-*-plain: at least 90 % of the poses change
+  the highest index wins a depth tie       colour-*-dup (copies in front of their originals change costs), colour-*-rev
+  an id ring that goes stale when it wraps colour-*: more records queued than 4 waves' rings hold
 """
 import numpy as np
 import pytest
@@ -316,3 +321,191 @@ def test_mutant_parent_box_padding(name):
     case = nn_case(name)
     assert any(s["missed"] for s in case.meta["search"].values())
     assert len(_changed(name, 2, cand="parent_box")) > 0
+
+
+# ---------------------------------------------------------------------------------------------
+# per-triangle colours (cost type 1): what the colour cases can tell apart, from the oracle alone
+# ---------------------------------------------------------------------------------------------
+
+def _colour_want(geom, variant):
+    key = ("colour", geom, variant)
+    if key not in _ORACLE:
+        _ORACLE[key] = nc.colour_case(geom, variant).oracle_costs(1)
+    return _ORACLE[key]
+
+
+def _differ(a, b):
+    """Poses whose costs differ between two results."""
+    return np.nonzero(~np.all([x.view(np.uint32) == y.view(np.uint32) for x, y in zip(a, b)], axis=0))[0]
+
+
+_PAIRS = {}
+
+
+def colour_pairs(geom, variant):
+    """nn_cases.gated_pairs with the neighbours of this module's brute force (`nearest`), computed once."""
+    if (geom, variant) not in _PAIRS:
+        case = nc.colour_case(geom, variant)
+        d2, idx = np.full(len(case.Q), np.inf, F32), np.full(len(case.Q), -1, np.int64)
+        for p in range(case.n):
+            sel = case.q_pose == p
+            d2[sel], idx[sel] = nearest(case, None, case.Q[sel])
+        _PAIRS[geom, variant] = nc.gated_pairs(case, (d2, idx))
+    return _PAIRS[geom, variant]
+
+
+@pytest.mark.parametrize("variant", nc.COLOUR_VARIANTS)
+@pytest.mark.parametrize("geom", nc.COLOUR_GEOMETRIES)
+def test_colour_pairs_restate_the_oracle_and_straddle_the_gate(geom, variant):
+    """The gated (observed point, triangle) pairs -- the triangle from the oracle's colour planes with the triangle
+    index in the colour bytes, the neighbour from the brute force above, the distance from the oracle -- give the
+    oracle's costs bit for bit, at the default threshold and at two others; between 15 % and 85 % of them are within
+    the gate; every pose has some."""
+    case = nc.colour_case(geom, variant)
+    pairs = colour_pairs(geom, variant)
+    assert 32 <= case.n <= 64 and len(case.obs_xyz) <= 21000 and not case.src_depth.any()
+    assert _same(nc.colour_costs_np(case, pairs, nc.COLOUR_THR), _colour_want(geom, variant))
+    for thr in (6.5, 31.0):
+        assert _same(nc.colour_costs_np(case, pairs, thr), case.oracle_costs(1, colour_thr=thr)), thr
+    share = float((pairs.d <= nc.COLOUR_THR).mean())
+    assert 0.15 <= share <= 0.85, share
+    assert len(np.unique(pairs.pose)) == int((pairs.num > 0).sum()) == case.n
+    assert not _same(_colour_want(geom, variant), case.oracle_costs(0))  # the gate matters
+
+
+@pytest.mark.parametrize("geom", nc.COLOUR_GEOMETRIES)
+def test_colour_table_rolled_by_one_triangle(geom):
+    """A sample coloured by the triangle before its own (a stream slot with its neighbour's entry of stri_orig): the
+    costs of at least 90 % of the poses that render anything change."""
+    case = nc.colour_case(geom, "plain")
+    want = _colour_want(geom, "plain")
+    cnt = case.bank.tris_model_count
+    rolled = nc._with_mesh(case, "rolled", [m.tris for m in case.bank.models],
+                           np.split(np.roll(case.bank.colors, 1, axis=0), np.cumsum(cnt)[:-1]), case.obs_rgb)
+    renders = int((want[0] != F32(-1.0)).sum())
+    changed = len(_differ(rolled.oracle_costs(1), want))
+    assert renders >= 32 and changed >= 0.9 * renders, (changed, renders)
+
+
+@pytest.mark.parametrize("geom", nc.COLOUR_GEOMETRIES)
+def test_colour_dup_copies_in_front_change_costs(geom):
+    """dup: at least 32 triangles per model appended once more with a colour on the other side of the gate.  Behind
+    their originals the copies change nothing (the lowest index wins a depth tie); in front of them they win, and
+    some pose's costs change: the highest index winning, or an id left by a later fragment, shows in this case."""
+    dup = nc.colour_case(geom, "dup")
+    for m, ids in enumerate(dup.meta["copied"]):
+        assert len(ids) >= 32 and len(np.unique(ids)) == len(ids), m
+    assert _same(_colour_want(geom, "dup"), _colour_want(geom, "plain"))
+    assert len(_differ(nc.colour_case(geom, "dup-front").oracle_costs(1), _colour_want(geom, "dup"))) > 0
+
+
+def depth_ties(geom):
+    """Rendered points whose minimum depth is reached by two or more triangles: the winner of the reversed mesh,
+    mapped back to the plain order, is the highest tied index, the plain winner the lowest.  Returns (ties, ties
+    between differently coloured triangles, those among the gated pairs)."""
+    plain, rev = nc.colour_case(geom, "plain"), nc.colour_case(geom, "rev")
+    hi = np.cumsum(plain.bank.tris_model_count)
+    lo = hi - plain.bank.tris_model_count
+    m = plain.pose_model[plain.q_pose]
+    low, high = nc.sample_triangles(plain), lo[m] + (hi[m] - 1 - nc.sample_triangles(rev))
+    assert (low <= high).all()
+    col = plain.bank.colors
+    tie = low != high
+    coloured = tie & (col[low] != col[high]).any(1)
+    return int(tie.sum()), int(coloured.sum()), int(coloured[colour_pairs(geom, "plain").q].sum())
+
+
+@pytest.mark.parametrize("geom", nc.COLOUR_GEOMETRIES)
+def test_colour_rev_differs_through_depth_ties(geom):
+    """rev renders the same depths; only the winners of depth ties change.  Its costs differ from the plain case's in
+    at least one pose: depth ties between differently coloured triangles occur among the gated samples and decide
+    costs."""
+    plain, rev = nc.colour_case(geom, "plain"), nc.colour_case(geom, "rev")
+    assert np.array_equal(_colour_want(geom, "plain")[0] == F32(-1.0), _colour_want(geom, "rev")[0] == F32(-1.0))
+    assert _same(plain.oracle_costs(0), rev.oracle_costs(0))  # the depth cost does not see the order
+    ties, coloured, gated = depth_ties(geom)
+    assert gated >= 8, (ties, coloured, gated)
+    assert len(_differ(_colour_want(geom, "rev"), _colour_want(geom, "plain"))) > 0
+
+
+def test_colour_id_ring_wraps():
+    """A wave's record ring holds kRecCap = 128 records, and ring_id with it.  Every model has a pose that queues more
+    than 128 triangles in every colour case; and in ties-TINY-s1 every model has a pose that queues more than 1.5
+    times 4 x 128 records (the box does in segments-s4 too), so that whichever way the triangles fall to the
+    workgroup's 4 waves, one wave's ring wraps.  (The window restated in float64 may differ from the kernel's by a
+    sample on a few triangles: hence the factor.  On the SMALL camera the can's largest pose queues about 540
+    records.)"""
+    for geom in nc.COLOUR_GEOMETRIES:
+        case = nc.colour_case(geom, "plain")
+        q = np.array([nc.queued_records(case, p) for p in range(case.n)])
+        for m in range(len(case.bank.models)):
+            tris, recs = q[case.pose_model == m].max(0)
+            assert tris > 128, (geom, m, tris)
+            if geom == "ties-TINY-s1" or (geom, m) == ("segments-s4", 0):
+                assert recs > 1.5 * 4 * 128, (geom, m, recs)
+
+
+# ---------------------------------------------------------------------------------------------
+# the threshold sweep: gated pairs whose distance, used as the threshold, pins the device's distance to the bit
+# ---------------------------------------------------------------------------------------------
+
+SWEEP_GEOM, SWEEP_MIN = "segments-s4", 64
+_SWEEP = {}
+
+
+def sweep_picks():
+    """Gated pairs of the plain SWEEP_GEOM case for the sweep of tests/test_gpu_colour.py, computed once: a list of
+    (pair, d as float32, the oracle's costs at threshold d, the oracle's costs at the float32 below d) and the number
+    of candidates that had to be replaced.  The distance is a float32 widened to double (its last operation is a
+    float square root), so the threshold d sits on it: at d the pair is within the gate, one float below it is
+    beyond.  Candidates: the pairs at SWEEP_MIN evenly spaced ranks of the sorted distances, the smallest and the
+    largest among them, then the median pair of every pose that has none yet.  A candidate for whose pose the
+    oracle's own costs do not differ between the two thresholds is replaced by the pair of the next rank."""
+    if "picks" in _SWEEP:
+        return _SWEEP["picks"]
+    case, pairs = nc.colour_case(SWEEP_GEOM, "plain"), colour_pairs(SWEEP_GEOM, "plain")
+    order = np.argsort(pairs.d, kind="stable")
+    cand = list(order[np.unique(np.linspace(0, len(order) - 1, SWEEP_MIN).round().astype(int))])
+    have = set(pairs.pose[cand])
+    for p in np.unique(pairs.pose):
+        if p not in have:
+            mine = order[pairs.pose[order] == p]
+            cand.append(mine[len(mine) // 2])
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    picks, used, replaced = [], set(), 0
+    for k in cand:
+        first = True
+        while True:
+            d = F32(pairs.d[k])
+            assert np.float64(d) == pairs.d[k] and np.isfinite(d)  # a float32, widened
+            if k not in used:
+                below = nc.step(d, -1)
+                hi, lo = case.oracle_costs(1, colour_thr=float(d)), case.oracle_costs(1, colour_thr=float(below))
+                if pairs.pose[k] in _differ(hi, lo):
+                    break
+            if first:
+                replaced, first = replaced + 1, False
+            k = order[(rank[k] + 1) % len(order)]
+        used.add(k)
+        picks.append((int(k), d, hi, lo))
+    _SWEEP["picks"] = (picks, replaced)
+    return _SWEEP["picks"]
+
+
+def test_colour_sweep_picks():
+    """At least 64 picked pairs; every pose with gated pairs has one; the smallest and the largest distance are
+    among them and the picks span the distances' quantiles; for every pick the oracle's costs of its pose differ
+    between the threshold on the distance and the float32 below it (sweep_picks replaces a candidate that fails)."""
+    pairs = colour_pairs(SWEEP_GEOM, "plain")
+    picks, replaced = sweep_picks()
+    ks = np.array([k for k, *_ in picks])
+    assert len(ks) >= SWEEP_MIN and len(np.unique(ks)) == len(ks)
+    assert set(pairs.pose[ks]) == set(pairs.pose)
+    ds = np.array([d for _, d, *_ in picks], np.float64)
+    assert ds.min() == pairs.d.min() and ds.max() == pairs.d.max()
+    q = np.searchsorted(np.sort(pairs.d), ds) / len(pairs.d)  # each decile of the distances has a pick
+    assert (np.bincount(np.minimum((q * 10).astype(int), 9), minlength=10) >= 3).all()
+    for k, d, hi, lo in picks:
+        assert pairs.pose[k] in _differ(hi, lo)
+    print(f"sweep: {len(picks)} pairs, {replaced} replaced, d in [{ds.min()}, {ds.max()}]")

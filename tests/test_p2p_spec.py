@@ -51,7 +51,7 @@ def test_library_and_header_carry_the_entry_points():
     for name in ("pcore_scene_projective",) + _native.EXPORTED_SYMBOLS_WITH_DIGITS:
         assert f"int {name}(" in header, name
         assert getattr(lib, name).argtypes is not None and getattr(lib, name).restype is not None, name
-    assert lib.pcore_abi_version() == 8
+    assert lib.pcore_abi_version() == 9
     assert "typedef struct pcore_p2p_icp_params" in header
     import ctypes
     assert ctypes.sizeof(_native.P2pIcpParams) == 16
