@@ -395,6 +395,26 @@ int pcore_depth_to_cloud_ex(pcore_ctx* ctx, const int32_t* d_depth, int32_t num_
 int pcore_select(pcore_ctx* ctx, const float* d_rc, const float* d_oc, const int32_t* d_pose_model,
                  int32_t num_poses, int64_t index_base, int32_t num_models, int64_t* d_keys, pcore_stream stream);
 
+/* The k best candidates per model instead of the minimum alone (no reference counterpart; the reference tracks the
+ * pre-ICP ranking beside the post-ICP one, lowest_preicp_cost_per_object, search_env.cpp:2567-2572): every pose gets
+ * exactly pcore_select's key.  Row m of d_topk (num_models x k int64, DEVICE) is a list of k keys in ascending order,
+ * padded with PCORE_KEY_NONE; the caller initialises it to PCORE_KEY_NONE.  After the call row m holds the k smallest
+ * keys of its previous content and the batch's keys of model m, ascending, so lists fold across batches (of disjoint
+ * index ranges) as pcore_select's keys do.  Keys carry the global index: they are distinct and totally ordered, equal
+ * costs order by lowest index first, and the result depends neither on scheduling nor on how the batch is cut nor on
+ * the order in which batches are folded.  With k = 1 the row equals pcore_select's d_keys[m].  Model ids outside [0,
+ * num_models) are ignored.  Lists of several ranks combine by taking the k smallest of their union.  Asynchronous on
+ * `stream`, no host readback.  Every argument is checked before the first launch (pcore_select's checks, with a last global
+ * index of at most 2^31 - 1, and 1 <= k <= PCORE_TOPK_MAX).  Per-context scratch for partial lists (at most 1024 x num_models x k keys) grows on first use; a
+ * capturing stream that would need that growth gets PCORE_E_STATE (run the call once before the capture), and the
+ * growth changes pcore_generation.  PCORE_TOPK_SLICE: the poses per partial list of a batch of at most 2^20 poses
+ * (diagnostics and tests; the results never depend on it). */
+#define PCORE_TOPK_MAX 64
+#define PCORE_TOPK_SLICE 1024
+int pcore_select_topk(pcore_ctx* ctx, const float* d_rc, const float* d_oc, const int32_t* d_pose_model,
+                      int32_t num_poses, int64_t index_base, int32_t num_models, int32_t k,
+                      int64_t* d_topk /* num_models x k, in/out */, pcore_stream stream);
+
 /* ADD / ADD-S of estimated against ground-truth poses over one model's points -- the YCB harness
  * metric: compare_clouds (sbpl_perception/src/scripts/tools/fat_dataset/
  * fat_pose_image.py:2020-2139) and pose_error.add / adi (fat_dataset/lib/utils/pose_error.py:72-108).

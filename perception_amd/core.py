@@ -499,6 +499,21 @@ class PoseCore:
             _ptr(keys, torch.int64, "keys"), _stream(stream)))
         return keys
 
+    def select_topk(self, rc: torch.Tensor, oc: torch.Tensor, pose_model: torch.Tensor, num_models: int, k: int,
+                    index_base: int = 0, topk: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """The k smallest select keys per model (pcore_select_topk) as a (num_models, k) int64 tensor: every row
+        ascending and padded with PCORE_KEY_NONE, folded into `topk` (initialised to PCORE_KEY_NONE) when given.
+        decode_keys works on it elementwise."""
+        if topk is None:
+            topk = torch.full((int(num_models), int(k)), _native.PCORE_KEY_NONE, dtype=torch.int64, device=rc.device)
+        elif tuple(topk.shape) != (int(num_models), int(k)):
+            raise ValueError(f"topk: expected shape {(int(num_models), int(k))}, got {tuple(topk.shape)}")
+        self._check(self.lib.pcore_select_topk(
+            self._h, _ptr(rc, torch.float32, "rc"), _ptr(oc, torch.float32, "oc"),
+            _ptr(pose_model, torch.int32, "pose_model"), int(rc.shape[0]), int(index_base), int(num_models), int(k),
+            _ptr(topk, torch.int64, "topk"), _stream(stream)))
+        return topk
+
     def count_within(self, queries: torch.Tensor, labels: torch.Tensor, radius_sq: torch.Tensor,
                      out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
         """IsValidPose neighbour counts (pcore_count_within): for every query (n x 3 float32), the points of its

@@ -8,6 +8,7 @@
 #include "pcore_gicp_math.h"
 #include "pcore_icp2d_math.h"
 #include "pcore_p2p_math.h"
+#include "pcore_topk.h"
 
 #include <algorithm>
 #include <climits>
@@ -137,6 +138,7 @@ struct pcore_ctx {
     uint64_t p2p_obs_serial = 0;      // the observation the scene below was built from (0: none)
     pcore_camera p2p_cam{};
     DevBuf<float4> p2p_pcd, p2p_normal;
+    DevBuf<int64_t> topk_part;  // pcore_select_topk: one partial list per (slice, model)
 };
 
 namespace {
@@ -345,6 +347,7 @@ void pcore_destroy(pcore_ctx* c) {
     (void)dev_free(c->metric_part); (void)dev_free(c->tri_rgb); (void)dev_free(c->render_tri);
     (void)dev_free(c->planar_cell_start); (void)dev_free(c->planar_pts);
     (void)dev_free(c->p2p_pcd); (void)dev_free(c->p2p_normal);
+    (void)dev_free(c->topk_part);
     for (hipEvent_t e : c->icp_ev) (void)hipEventDestroy(e);
     delete c;
 }
@@ -1582,6 +1585,25 @@ int pcore_select(pcore_ctx* c, const float* d_rc, const float* d_oc, const int32
     if (num_poses == 0) return PCORE_OK;
     HIPC(c, hipSetDevice(c->device));
     HIPC(c, launch_select(d_rc, d_oc, d_pose_model, num_poses, index_base, num_models, d_keys, (hipStream_t)stream));
+    return PCORE_OK;
+}
+
+int pcore_select_topk(pcore_ctx* c, const float* d_rc, const float* d_oc, const int32_t* d_pose_model, int32_t num_poses,
+                      int64_t index_base, int32_t num_models, int32_t k, int64_t* d_topk, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    // pcore_select's checks; the last global index may be 2^31 - 1, all that the key's 31 index bits hold
+    if (num_poses < 0 || num_models <= 0 || index_base < 0 || index_base + num_poses > 0x80000000LL ||
+        (num_poses > 0 && (!d_rc || !d_oc || !d_pose_model || !d_topk)))
+        return fail(c, PCORE_E_INVALID_ARG, "select_topk: bad arguments");
+    if (k < 1 || k > PCORE_TOPK_MAX) return fail(c, PCORE_E_INVALID_ARG, "select_topk: k must lie in [1, PCORE_TOPK_MAX]");
+    if (num_poses == 0) return PCORE_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPC(c, hipSetDevice(c->device));
+    const size_t need = (size_t)topk_slices(num_poses) * (size_t)num_models * (size_t)k;
+    if (int rc = refuse_setup_in_capture(c, "select_topk", "the partial lists", c->topk_part.n < need || !c->topk_part.p, s))
+        return rc;
+    HIPC(c, reserve_gen(c, c->topk_part, need));
+    HIPC(c, launch_select_topk(d_rc, d_oc, d_pose_model, num_poses, index_base, num_models, k, c->topk_part.p, d_topk, s));
     return PCORE_OK;
 }
 

@@ -70,6 +70,20 @@ def allreduce_min_keys(keys: torch.Tensor) -> torch.Tensor:
     return keys
 
 
+def allgather_topk_keys(topk: torch.Tensor) -> torch.Tensor:
+    """The exchange of the per-model shortlists (PoseCore.select_topk): every rank's (M, k) ascending key lists are
+    all-gathered and each model keeps the k smallest of their union, ascending -- the list one process would have
+    computed over all shards, the same on every rank.  Returns its argument unchanged when no exchange runs."""
+    if not exchange_active():
+        return topk
+    # gloo gathers host tensors only (the rehearsal backend; the lists are M x k keys); RCCL gathers on the device
+    mine = topk.cpu() if topk.is_cuda and dist.get_backend() == "gloo" else topk.contiguous()
+    parts = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, mine)
+    merged = torch.sort(torch.cat(parts, dim=1), dim=1).values  # keys carry the global index: a total order
+    return merged[:, :topk.shape[1]].contiguous().to(topk.device)
+
+
 def allreduce_min_keys_async(keys: torch.Tensor) -> Optional["dist.Work"]:
     """The same exchange, returned as a work handle (None on one process).  The caller waits on it before
     reading or rewriting `keys`; meanwhile the next batch's kernels run beside the collective (RCCL runs on

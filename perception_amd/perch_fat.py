@@ -51,6 +51,8 @@ PERCH_PARAM_DEFAULTS = {
     "max_icp_iterations": ("max_icp_iterations", 10),
     "icp_max_correspondence": ("icp_max_correspondence", 0.05),
     "use_model_specific_search_resolution": ("use_model_specific_search_resolution", False),
+    # a build extension (no reference counterpart): the staged search's shortlist per model, 0 = refine every state
+    "icp_top_k": ("icp_top_k", 0),
 }
 # object_recognizer.cpp:57-77
 CAMERA_DEFAULTS = {"camera_width": 640, "camera_height": 480, "camera_fx": 576.09757860, "camera_fy": 576.09757860,

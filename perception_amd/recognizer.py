@@ -26,11 +26,12 @@ import torch
 
 from . import io as pio
 from ._native import (COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, P2P_MAX_DIST_DIFF, P2P_MAX_ITER,
-                      P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE)
+                      P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE, PCORE_TOPK_MAX)
 from .core import PoseCore, decode_keys
-from .distributed import allreduce_min_keys, shard_range
+from .distributed import allgather_topk_keys, allreduce_min_keys, shard_range
 from .model import (Model, chain_matmul_batch, compute_proj, init_from_eigen_batch, matmul_lazy, pose_matrix_batch,
                     quat_from_matrix_eigen_batch, so3_log_batch)
+from .staged import refine_shortlist, select_refined, shortlist_members
 
 # cam_to_body (search_env.cpp:1536-1539)
 CAM_TO_BODY = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1]], np.float64)
@@ -71,6 +72,10 @@ class PerchParams:
     p2p_relative_fitness: float = P2P_REL_FITNESS
     p2p_relative_rmse: float = P2P_REL_RMSE
     p2p_max_dist_diff: float = P2P_MAX_DIST_DIFF
+    # the staged search (a build extension, INTEGRATION.md "Staged search"): with use_icp and icp_type 3 or 4, score
+    # every state without ICP, refine only the icp_top_k best per model (1 .. 64) and select among the refined;
+    # 0 = the reference's flow, every state refined
+    icp_top_k: int = 0
 
 
 @dataclass
@@ -472,10 +477,57 @@ class ObjectRecognizer:
         3-DoF search has such a stage (TabletopRecognizer); here the states pass through."""
         return states, poses, 0.0
 
+    # -- the staged search (a build extension; INTEGRATION.md "Staged search") ----------------------
+    def _staged_top_k(self, inp: RecognitionInput) -> int:
+        """The shortlist length per model when this search runs staged, else 0 (the reference's flow)."""
+        k, p = int(self.params.icp_top_k), self.params
+        if k == 0:
+            return 0
+        if not 1 <= k <= PCORE_TOPK_MAX:
+            raise ValueError(f"icp_top_k must lie in [0, {PCORE_TOPK_MAX}], got {k}")
+        if p.icp_type == 0:
+            raise ValueError("icp_top_k: the planar ICP of icp_type 0 refines the states before they are scored; "
+                             "the staged search needs icp_type 3 or 4")
+        return k if inp.use_icp and p.icp_type in (3, 4) else 0
+
+    def _staged_refine(self, k: int, lo: int, hi: int, K: int, keys: torch.Tensor, shard):
+        """Stages 2 and 3 of the staged search over a shard already scored without ICP: the k best pre-ICP keys per
+        model (select_topk, exchanged between the ranks), ICP and re-scoring of the shortlist members of [lo, hi) only,
+        and the selection among the refined rows into `keys`.  The shard's costs, adjusted poses and iterations are
+        overwritten at the refined rows and keep their pre-ICP values elsewhere.  `shard` is None for an empty shard
+        (the rank still takes part in the exchange).  Returns PoseCore.stats of the GICP call, or None without one."""
+        p = self.params
+        topk = torch.full((K, k), PCORE_KEY_NONE, dtype=torch.int64, device=self.device)
+        if shard is not None:
+            poses, pm, pl, tot, cost_type, rc, oc, df, adj_all, iters = shard
+            self.core.select_topk(rc, oc, pm, K, k, index_base=lo, topk=topk)
+        topk = allgather_topk_keys(topk)
+        self.last_shortlist = topk  # (K, k) global pre-ICP keys, the same on every rank (diagnostics)
+        if shard is None:
+            return None
+        members = shortlist_members(topk, lo, hi)
+        kw = dict(cost_type=cost_type, stride=p.gpu_stride, depth_factor=p.gpu_depth_factor,
+                  sensor_resolution=p.sensor_resolution, occlusion_threshold=p.gpu_occlusion_threshold)
+        if p.icp_type == 3:
+            icp_kw = dict(k=p.icp_k, max_iterations=p.icp_max_iterations, rotation_epsilon=p.icp_rotation_epsilon,
+                          transformation_epsilon=p.icp_transformation_epsilon)
+        else:
+            icp_kw = dict(max_iterations=p.p2p_max_iterations, relative_fitness=p.p2p_relative_fitness,
+                          relative_rmse=p.p2p_relative_rmse, max_dist_diff=p.p2p_max_dist_diff)
+        refined = refine_shortlist(self.core, members, poses, pm, pl, tot, p.icp_type, kw, icp_kw)
+        if refined is None:  # no shortlist member in this shard: no call, the keys stay empty
+            return None
+        select_refined(self.core, refined, pm, K, lo, keys)
+        sub, a, it, r, o, d = refined
+        rc[sub], oc[sub], df[sub], adj_all[sub], iters[sub] = r, o, d, a, it
+        torch.cuda.synchronize(self.device)
+        return self.core.stats(reset=True) if p.icp_type == 3 else None
+
     # -- ComputeGreedyRenderPoses (search_env.cpp:2462-2651) ----------------------------------------
     def compute_greedy_render_poses(self, inp: RecognitionInput):
         t0 = time.perf_counter()
         p = self.params
+        staged = self._staged_top_k(inp)
         self._check_state_hooks()
         if self._device_state_path:
             dstates = self._successor_states_device(inp)
@@ -526,7 +578,11 @@ class ObjectRecognizer:
             # test_gpu_fullsize.py::test_c2_permutation_and_chunking_invariance) and the context chunks GICP by
             # its own scratch budget, so the whole shard goes down in one call.
             ti = time.perf_counter()
-            if p.icp_type == 3 and inp.use_icp:
+            if staged:  # stage 1: every state's pre-ICP cost; the shortlist and the refinement follow below
+                self.core.evaluate(poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride,
+                                   depth_factor=p.gpu_depth_factor, sensor_resolution=p.sensor_resolution,
+                                   occlusion_threshold=p.gpu_occlusion_threshold, out=(rc, oc, df))
+            elif p.icp_type == 3 and inp.use_icp:
                 self.core.evaluate_icp(poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride,
                                        depth_factor=p.gpu_depth_factor, sensor_resolution=p.sensor_resolution,
                                        occlusion_threshold=p.gpu_occlusion_threshold, k=p.icp_k,
@@ -548,13 +604,21 @@ class ObjectRecognizer:
                                    select=(keys, lo, K))
             torch.cuda.synchronize(self.device)
             gpu_s = time.perf_counter() - ti
-            if p.icp_type == 3 and inp.use_icp:
+            if p.icp_type == 3 and inp.use_icp and not staged:
                 # gpu_stats of the call (renderer.cu:1736-1739): the GICP stage's own time and the peak memory;
                 # search_env.cpp:1715-1716 adds icp_runtime (seconds) to env_stats_.icp_time
                 st = self.core.stats(reset=True)
                 icp_time = float(st["icp_runtime"])
                 peak_mb = st["peak_memory_usage"]  # gpu_stats.peak_memory_usage (MB)
             self._last_costs_dev = (rc, oc, df)  # read back only on request (_last_costs)
+        if staged:  # every rank takes part in the shortlist exchange, with or without a shard
+            ti = time.perf_counter()
+            shard = (poses, pm, pl, tot, cost_type, rc, oc, df, adj_all, iters) if n > 0 else None
+            st = self._staged_refine(staged, lo, hi, K, keys, shard)
+            gpu_s += time.perf_counter() - ti
+            if st is not None:
+                icp_time = float(st["icp_runtime"])
+                peak_mb = st["peak_memory_usage"]
         allreduce_min_keys(keys)
         cost, idx = decode_keys(keys)
         # winning adjusted poses: the owning rank contributes, the others add zeros

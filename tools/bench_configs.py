@@ -8,6 +8,8 @@ multi-GPU configs).  Prints one JSON line per config.  Not the driver's bench (b
       and GICP on the same states (not in the default list: --configs c1_planar)
   c1_p2p  the same 20,000 states: the point-to-plane projective ICP stage beside the planar ICP stage and GICP
   c3_p2p  C3's batch through evaluate_p2p (point-to-plane ICP + re-score) beside evaluate_icp (GICP + re-score)
+  c3_topk  C3's batch through the staged search (evaluate + select_topk + evaluate_icp on the K best per model + select)
+      for K = 1, 4, 16, 64 beside the full evaluate_icp + select
   C2  1 mesh, 10k poses, render + score, 640x480
   C3  5 objects, 50k poses, render + GICP + re-render + score, 640x480 (+ argmin vs GT)
   C4  21 objects, 200k poses over 8 GPUs -> 25k poses per GPU, render + score
@@ -349,6 +351,60 @@ def run_c3_p2p(per_model=10000, runs=5):
                       "gicp_iters_mean": float(res["gicp"][1].float().mean().item())}), flush=True)
 
 
+def run_c3_topk(per_model=10000, runs=5, ks=(1, 4, 16, 64)):
+    """c3_topk: C3's batch (5 objects, 50k 6-DoF poses) through the staged search (evaluate + select_topk + evaluate_icp
+    on the shortlist + select; perception_amd/staged.py) for each K, beside the full evaluate_icp + select on the same
+    context in the same job -- `runs` alternating runs each after one warm-up, medians; select_topk alone too."""
+    from perception_amd.staged import staged_step
+    w = workloads.build(names=C3_NAMES, poses_per_model=per_model, cam=syn.CAM_640)
+    n = int(w.poses.shape[0])
+    args = (w.poses, w.pose_model, w.pose_label, w.pose_obs_total)
+    res = {}
+
+    def full():
+        keys = torch.full((w.num_models,), PCORE_KEY_NONE, dtype=torch.int64, device=w.poses.device)
+        out = w.core.evaluate_icp(*args, stride=w.stride)
+        w.core.select(out[2], out[3], w.pose_model, w.num_models, keys=keys)
+        res["full"] = (keys, out)
+
+    def staged(k):
+        def fn():
+            res[k] = staged_step(w.core, *args, w.num_models, k, eval_kw=dict(stride=w.stride))
+        return fn
+
+    pre = w.core.evaluate(*args, stride=w.stride)
+    lists = {k: torch.full((w.num_models, k), PCORE_KEY_NONE, dtype=torch.int64, device=w.poses.device) for k in ks}
+
+    def topk_only(k):
+        def fn():
+            lists[k].fill_(PCORE_KEY_NONE)
+            w.core.select_topk(pre[0], pre[1], w.pose_model, w.num_models, k, topk=lists[k])
+        return fn
+
+    fns = {"full": full, **{f"staged_{k}": staged(k) for k in ks}, **{f"topk_{k}": topk_only(k) for k in ks}}
+    for fn in fns.values():  # warm-up: scratch, grids, target covariances
+        _once(fn)
+    t = {name: [] for name in fns}
+    for _ in range(runs):  # alternating
+        for name, fn in fns.items():
+            t[name].append(_once(fn))
+    med = {name: float(np.median(v)) for name, v in t.items()}
+    full_cost, full_idx = decode_keys(res["full"][0])
+    out = {"config": "c3_topk", "poses": n, "models": w.num_models, "stride": w.stride, "runs": runs,
+           "full_s": med["full"], "full_poses_per_s": n / med["full"], "full_s_all": t["full"],
+           "full_argmin_index": [int(i) for i in full_idx], "full_argmin_cost": [int(c) for c in full_cost],
+           "gt_index": [int(i) for i in w.gt_index], "staged": []}
+    for k in ks:
+        keys, _, refined, _ = res[k]
+        cost, idx = decode_keys(keys)
+        out["staged"].append({"k": k, "s_per_step": med[f"staged_{k}"], "poses_per_s": n / med[f"staged_{k}"],
+                              "select_topk_s": med[f"topk_{k}"], "poses_refined": 0 if refined is None else int(len(refined[0])),
+                              "full_over_staged": med["full"] / med[f"staged_{k}"], "s_all": t[f"staged_{k}"],
+                              "argmin_index": [int(i) for i in idx], "argmin_cost": [int(c) for c in cost],
+                              "same_winner_as_full": [bool(a == b) for a, b in zip(idx, full_idx)]})
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4,C5")
@@ -366,6 +422,8 @@ def main():
         run_c1_p2p(nxy=max(2, int(round(50 * sc ** 0.5))))
     if "c3_p2p" in sel:
         run_c3_p2p(per_model=max(1, int(10000 * sc)))
+    if "c3_topk" in sel:
+        run_c3_topk(per_model=max(1, int(10000 * sc)))
     if "C2" in sel:
         run("C2", ["003_cracker_box"], int(10000 * sc), syn.CAM_640, False, a.steps, a.warmup)
     if "C3" in sel:

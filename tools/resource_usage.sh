@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers, spills, scratch and LDS of the GICP / fused / cloud / planar ICP / point-to-plane ICP kernels as the compiler
+# Registers, spills, scratch and LDS of the GICP / fused / cloud / planar ICP / point-to-plane ICP / top-K kernels as the compiler
 # reports them (no GPU needed), over every source of build.SOURCES:
 #   tools/resource_usage.sh [extra hipcc flags, e.g. -DPCORE_GICP_LDS_ROUNDS=1]
 # (tools/isa_diff.py prints the same figures for every kernel beside a comparison with another tree.)
@@ -10,7 +10,7 @@ for SRC in $(python -c "from perception_amd import build; print(' '.join(build.S
     -Rpass-analysis=kernel-resource-usage 2>&1 | python -c "
 import re, sys
 cur = None
-KERNELS = ('gicp_kernel', 'fused_cost', 'render_cloud_kernel', 'window_probe_kernel', 'covariance_kernel', 'planar_icp', 'p2p_icp', 'scene_kernel')
+KERNELS = ('gicp_kernel', 'fused_cost', 'render_cloud_kernel', 'window_probe_kernel', 'covariance_kernel', 'planar_icp', 'p2p_icp', 'scene_kernel', 'topk_')
 for l in sys.stdin:
     m = re.search(r'remark: Function Name: (\S+)', l)
     if m:
