@@ -75,6 +75,40 @@ def label_covs(case, six=True):
     return cov
 
 
+def oracle_recognizer_pipeline(rec, inp, sc, icp):
+    """The oracle's side of ObjectRecognizer.localize_objects_greedy_render on the recognizer's own candidate states
+    (after set_input): stage COST (with GICP when icp) and the selection.  -> (adjusted poses (N, 16), best cost and
+    best index per model)."""
+    K = len(inp.model_names)
+    p = rec.params
+    states = rec.generate_successor_states(inp)
+    mats = rec._pose_in_cam(states)
+    pm = np.array([s[0] for s in states], np.int32)
+    pl = np.array([s[1] for s in states], np.int32)
+    xyz, lab = rec.obs_xyz_host, rec.obs_label_host
+    order = np.argsort(lab, kind="stable")
+    oxyz, olab = xyz[order], lab[order]
+    ls = np.array([np.searchsorted(olab, L, "left") for L in range(K)], np.int32)
+    le = np.array([np.searchsorted(olab, L, "right") for L in range(K)], np.int32)
+    tot = rec.segmented_count[pl]
+    src = sc.src_depth_cm
+    if icp:
+        ocov = np.zeros((len(oxyz), 6))
+        for L in range(K):
+            ocov[ls[L]:le[L]] = oracle.covariances(oxyz[ls[L]:le[L]])
+        adj, _, rc, oc, df = oracle.evaluate_icp(sc.bank.tris, sc.bank.tris_model_count, mats, pm, pl, sc.width,
+                                                 sc.height, sc.proj, src, sc.mask, 1.0, p.gpu_stride, sc.cx, sc.cy,
+                                                 sc.fx, sc.fy, 100.0, oxyz, ocov, ls, le, tot, 2, True,
+                                                 p.sensor_resolution)
+    else:
+        rc, oc, df = oracle.evaluate(sc.bank.tris, sc.bank.tris_model_count, mats, pm, pl, sc.width, sc.height,
+                                     sc.proj, src, sc.mask, 1.0, p.gpu_stride, sc.cx, sc.cy, sc.fx, sc.fy, 100.0, oxyz,
+                                     ls, le, tot, 2, True, p.sensor_resolution)
+        adj = mats
+    bc, bi = oracle.select(rc, oc, pm, K)
+    return adj, bc, bi
+
+
 def grid_clouds(cam, s):
     """Clouds unprojected from a stride-s sample grid of the camera (what render_cloud writes): tilted planes, a step
     (a depth discontinuity inside the neighbourhoods), 24 to 1,000 points -- the last one's window (40 x 25 cells) is

@@ -13,7 +13,7 @@ from perception_amd.core import PoseCore
 from perception_amd.model import init_from_eigen_batch, matrix_to_quat_xyzw
 from perception_amd.recognizer import (CameraIntrinsics, ModelMetaData, ObjectRecognizer, PerchParams,
                                        RecognitionInput)
-from tests.helpers import oracle_render_fn
+from tests.helpers import oracle_recognizer_pipeline, oracle_render_fn
 
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -62,31 +62,9 @@ def test_localize_objects_greedy_render_matches_oracle_pipeline(tmp_path, icp):
                            rendered_root_dir=str(tmp_path), use_icp=int(icp))
     res = rec.localize_objects_greedy_render(inp)
     assert res.model_names == names
-    # oracle pipeline on the same candidate states
-    states = rec.generate_successor_states(inp)
-    mats = rec._pose_in_cam(states)
-    pm = np.array([s[0] for s in states], np.int32)
-    pl = np.array([s[1] for s in states], np.int32)
-    xyz, lab = rec.obs_xyz_host, rec.obs_label_host
-    order = np.argsort(lab, kind="stable")
-    oxyz, olab = xyz[order], lab[order]
-    ls = np.array([np.searchsorted(olab, L, "left") for L in range(3)], np.int32)
-    le = np.array([np.searchsorted(olab, L, "right") for L in range(3)], np.int32)
-    tot = rec.segmented_count[pl]
-    src = sc.src_depth_cm
-    if icp:
-        ocov = np.zeros((len(oxyz), 6))
-        for L in range(3):
-            ocov[ls[L]:le[L]] = oracle.covariances(oxyz[ls[L]:le[L]])
-        adj, _, rc, oc, df = oracle.evaluate_icp(sc.bank.tris, sc.bank.tris_model_count, mats, pm, pl, sc.width,
-                                                 sc.height, sc.proj, src, sc.mask, 1.0, 8, sc.cx, sc.cy, sc.fx, sc.fy,
-                                                 100.0, oxyz, ocov, ls, le, tot, 2, True, 0.01)
-    else:
-        rc, oc, df = oracle.evaluate(sc.bank.tris, sc.bank.tris_model_count, mats, pm, pl, sc.width, sc.height,
-                                     sc.proj, src, sc.mask, 1.0, 8, sc.cx, sc.cy, sc.fx, sc.fy, 100.0, oxyz, ls, le,
-                                     tot, 2, True, 0.01)
-        adj = mats
-    bc, bi = oracle.select(rc, oc, pm, 3)
+    # oracle pipeline on the same candidate states (stride 8, sensor resolution 0.01: the recognizer's defaults)
+    assert (rec.params.gpu_stride, rec.params.sensor_resolution) == (8, 0.01)
+    adj, bc, bi = oracle_recognizer_pipeline(rec, inp, sc, icp)
     assert res.indices == [int(i) for i in bi if i >= 0]
     assert res.costs == [int(c) for c, i in zip(bc, bi) if i >= 0]
     for k, i in enumerate(res.indices):
