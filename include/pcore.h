@@ -270,6 +270,37 @@ int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_
                            float fx, float fy, float cx, float cy, const pcore_p2p_icp_params* icp, float* d_out_T,
                            float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream);
 
+/* Point-to-plane ICP against a nearest-neighbour scene (cuda_icp: ICP_Point2Plane_cuda over Scene_nn,
+ * pcd_scene.h:48-137): each point is paired with the nearest scene point in 3-D, so the correspondence follows the
+ * nearest surface across a depth edge where the projective scene pairs it with whatever its own pixel shows.  The
+ * reference's kd-tree over the whole cloud is replaced by an exact search over the pixels within `window` of the
+ * point's own pixel (the lowest pixel index wins on equal distances), which is the nearest neighbour of the whole
+ * image whenever every pixel that can hold a point within max_dist_diff lies inside that window: DESIGN.md section 5,
+ * "Nearest-neighbour scene".  The loop is pcore_icp_point2plane's.  The source depth is integer centimetres, so the
+ * scene is quantised at the size of the default radius. */
+typedef struct pcore_nn_icp_params {
+    int32_t max_iterations;     /* 30 */
+    float   relative_fitness;   /* 1e-5 */
+    float   relative_rmse;      /* 1e-5 */
+    float   max_dist_diff;      /* 0.01 m, the search radius (Scene_nn, pcd_scene.h:49); > 0 */
+    int32_t window;             /* 32 pixels, the search window's half-width; 0 ... 128 */
+} pcore_nn_icp_params;
+
+/* pcore_icp_point2plane with the nearest-neighbour scene: the same arguments, outputs, scene cache, scratch budget
+ * (PCORE_P2P_SCRATCH_BYTES), chunking and capture rule.  Every argument is checked before the first launch. */
+int pcore_icp_point2plane_nn(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_model,
+                             const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* params,
+                             const pcore_nn_icp_params* icp, float* d_out_T, float* d_out_fitness, float* d_out_rmse,
+                             int32_t* d_out_iters, float* d_out_poses, pcore_stream stream);
+
+/* Test hook (no reference counterpart): pcore_debug_p2p_clouds over the nearest-neighbour scene.  The scene's points
+ * must be dep2pcd of a centimetre depth image under the given camera (as pcore_scene_projective writes them): the
+ * search skips pixels whose point cannot lie within the radius. */
+int pcore_debug_p2p_nn_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_t seg_stride, int32_t num_segs,
+                              const float* d_scene_pcd4, const float* d_scene_normal4, int32_t width, int32_t height,
+                              float fx, float fy, float cx, float cy, const pcore_nn_icp_params* icp, float* d_out_T,
+                              float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream);
+
 /* Test hook (no reference counterpart): stage CLOUD of every pose into caller-made slots, as the ICP entry points
  * render their source clouds -- pose i's points (x, y, z, 0) in the reference's compaction order (row-major stride
  * samples, compute_point_clouds.cuh:290-346) at d_out_xyzw + 4 i ws hs, their number in d_out_count[i]; ws = W / stride,

@@ -40,7 +40,8 @@ EXPORTED_SYMBOLS = (
     "pcore_select_topk",
 )
 # declared in include/pcore.h too; kept apart because tests/test_abi.py's symbol pattern stops at a digit
-EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds", "pcore_debug_rgb2lab")
+EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds", "pcore_debug_rgb2lab",
+                                "pcore_icp_point2plane_nn", "pcore_debug_p2p_nn_clouds")
 
 
 class PcoreError(RuntimeError):
@@ -97,11 +98,21 @@ class P2pIcpParams(ctypes.Structure):
                 ("relative_rmse", ctypes.c_float), ("max_dist_diff", ctypes.c_float)]
 
 
+class NnIcpParams(ctypes.Structure):
+    """pcore_nn_icp_params (include/pcore.h)."""
+    _fields_ = [("max_iterations", ctypes.c_int32), ("relative_fitness", ctypes.c_float),
+                ("relative_rmse", ctypes.c_float), ("max_dist_diff", ctypes.c_float), ("window", ctypes.c_int32)]
+
+
 # ICPConvergenceCriteria (cuda_icp icp.h:39-51) and Scene_projective's max_dist_diff (depth_scene.h:9)
 P2P_MAX_ITER = 30
 P2P_REL_FITNESS = 1e-5
 P2P_REL_RMSE = 1e-5
 P2P_MAX_DIST_DIFF = 0.1
+# Scene_nn's radius (pcd_scene.h:49) and the search window's half-width in pixels (DESIGN.md section 5)
+NN_MAX_DIST_DIFF = 0.01
+NN_WINDOW = 32
+NN_MAX_WINDOW = 128
 
 # GetICPAdjustedPose's settings (search_env.cpp:6235-6396; env_config.yaml max_icp_iterations, icp_max_correspondence)
 PLANAR_MAX_ITER = 20
@@ -188,6 +199,11 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
                                             ctypes.POINTER(P2pIcpParams), vp, vp, vp, vp, vp, vp]
         L.pcore_debug_p2p_clouds.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, f32, f32, f32, f32,
                                              ctypes.POINTER(P2pIcpParams), vp, vp, vp, vp, vp]
+    if hasattr(L, "pcore_icp_point2plane_nn"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_icp_point2plane_nn.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(EvalParams),
+                                               ctypes.POINTER(NnIcpParams), vp, vp, vp, vp, vp, vp]
+        L.pcore_debug_p2p_nn_clouds.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, f32, f32, f32, f32,
+                                                ctypes.POINTER(NnIcpParams), vp, vp, vp, vp, vp]
     if hasattr(L, "pcore_debug_render_clouds"):  # absent from older A/B builds (PCORE_LIB)
         L.pcore_debug_render_clouds.argtypes = [vp, vp, vp, vp, i32, ctypes.POINTER(EvalParams), vp, vp, vp]
     if hasattr(L, "pcore_debug_colour_distance"):  # absent from older A/B builds (PCORE_LIB)

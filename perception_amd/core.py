@@ -320,12 +320,17 @@ class PoseCore:
                         cost_type: int = _native.COST_DEPTH_6DOF, stride: int = 8, depth_factor: float = 100.0,
                         occlusion_threshold: float = 1.0, max_iterations: int = _native.P2P_MAX_ITER,
                         relative_fitness: float = _native.P2P_REL_FITNESS,
-                        relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
-                        out=None, out_poses: Optional[torch.Tensor] = None, stream=None):
+                        relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: Optional[float] = None,
+                        out=None, out_poses: Optional[torch.Tensor] = None, stream=None, scene: str = "projective",
+                        window: int = _native.NN_WINDOW):
         """Point-to-plane ICP of every pose's rendered stride-sample cloud against the projective scene of the
         observation's source depth (pcore_icp_point2plane); pose_label selects the 6-DoF source occlusion, None the
         3-DoF one.  Returns (T (N, 16) float32, fitness (N,), rmse (N,), iterations (N,) int32) on the GPU; with
-        out_poses (N, 16) also writes concatenate_transforms(T, pose) there."""
+        out_poses (N, 16) also writes concatenate_transforms(T, pose) there.  scene="nn" pairs each point with its
+        nearest scene point within max_dist_diff among the pixels within `window` of its own (pcore_icp_point2plane_nn);
+        max_dist_diff defaults to 0.1 for the projective scene and to 0.01 for the nearest-neighbour one."""
+        fn, ip = self._p2p_call(scene, "pcore_icp_point2plane", max_iterations, relative_fitness, relative_rmse,
+                                max_dist_diff, window)
         n = int(poses.shape[0])
         dev = poses.device
         if out is None:
@@ -333,22 +338,41 @@ class PoseCore:
                    torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
         T, fitness, rmse, iters = out
         p = EvalParams(int(cost_type), 0, int(stride), float(depth_factor), 0.0, float(occlusion_threshold), 0.0)
-        ip = P2pIcpParams(int(max_iterations), float(relative_fitness), float(relative_rmse), float(max_dist_diff))
-        self._check(self.lib.pcore_icp_point2plane(
+        self._check(fn(
             self._h, _ptr(poses, torch.float32, "poses"), _ptr(pose_model, torch.int32, "pose_model"),
             _ptr(pose_label, torch.int32, "pose_label"), n, ctypes.byref(p), ctypes.byref(ip),
             _ptr(T, torch.float32, "T"), _ptr(fitness, torch.float32, "fitness"), _ptr(rmse, torch.float32, "rmse"),
             _ptr(iters, torch.int32, "iterations"), _ptr(out_poses, torch.float32, "out_poses"), _stream(stream)))
         return T, fitness, rmse, iters
 
+    def _p2p_call(self, scene, name, max_iterations, relative_fitness, relative_rmse, max_dist_diff, window):
+        """The entry point and the parameter struct of a point-to-plane call against the named scene."""
+        if scene == "projective":
+            d = _native.P2P_MAX_DIST_DIFF if max_dist_diff is None else max_dist_diff
+            return getattr(self.lib, name), P2pIcpParams(int(max_iterations), float(relative_fitness),
+                                                         float(relative_rmse), float(d))
+        if scene != "nn":
+            raise ValueError(f"scene must be 'projective' or 'nn', not {scene!r}")
+        d = _native.NN_MAX_DIST_DIFF if max_dist_diff is None else max_dist_diff
+        name = {"pcore_icp_point2plane": "pcore_icp_point2plane_nn", "pcore_debug_p2p_clouds": "pcore_debug_p2p_nn_clouds"}[name]
+        return getattr(self.lib, name), _native.NnIcpParams(int(max_iterations), float(relative_fitness),
+                                                            float(relative_rmse), float(d), int(window))
+
+    def debug_p2p_clouds(self, *args, **kw):
+        """p2p_clouds under the C entry point's name."""
+        return self.p2p_clouds(*args, **kw)
+
     def p2p_clouds(self, xyzw: torch.Tensor, seg_cnt: torch.Tensor, scene_pcd4: torch.Tensor,
                    scene_normal4: torch.Tensor, fx: float, fy: float, cx: float, cy: float,
                    max_iterations: int = _native.P2P_MAX_ITER, relative_fitness: float = _native.P2P_REL_FITNESS,
-                   relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
-                   stream=None):
+                   relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: Optional[float] = None,
+                   stream=None, scene: str = "projective", window: int = _native.NN_WINDOW):
         """pcore_debug_p2p_clouds: the point-to-plane ICP kernel over caller-made slots xyzw (S, cap, 4) float32 with
         seg_cnt (S,) int32 points each (moved in place) and a caller-made scene (H, W, 4) + (H, W, 4).  Returns (T
-        (S, 16), fitness, rmse, iterations)."""
+        (S, 16), fitness, rmse, iterations).  scene="nn": pcore_debug_p2p_nn_clouds, whose scene points must be dep2pcd
+        of a centimetre depth image under the camera given."""
+        fn, ip = self._p2p_call(scene, "pcore_debug_p2p_clouds", max_iterations, relative_fitness, relative_rmse,
+                                max_dist_diff, window)
         s, cap = int(xyzw.shape[0]), int(xyzw.shape[1])
         h, w = int(scene_pcd4.shape[0]), int(scene_pcd4.shape[1])
         dev = xyzw.device
@@ -356,15 +380,14 @@ class PoseCore:
         fitness = torch.empty(s, dtype=torch.float32, device=dev)
         rmse = torch.empty(s, dtype=torch.float32, device=dev)
         iters = torch.empty(s, dtype=torch.int32, device=dev)
-        ip = P2pIcpParams(int(max_iterations), float(relative_fitness), float(relative_rmse), float(max_dist_diff))
-        rc = self.lib.pcore_debug_p2p_clouds(
+        rc = fn(
             _ptr(xyzw, torch.float32, "xyzw"), _ptr(seg_cnt, torch.int32, "seg_cnt"), cap, s,
             _ptr(scene_pcd4, torch.float32, "scene_pcd4"), _ptr(scene_normal4, torch.float32, "scene_normal4"), w, h,
             float(fx), float(fy), float(cx), float(cy), ctypes.byref(ip), _ptr(T, torch.float32, "T"),
             _ptr(fitness, torch.float32, "fitness"), _ptr(rmse, torch.float32, "rmse"),
             _ptr(iters, torch.int32, "iterations"), _stream(stream))
         if rc != _native.PCORE_OK:
-            raise PcoreError(rc, "pcore_debug_p2p_clouds failed")
+            raise PcoreError(rc, f"{fn.__name__} failed")
         return T, fitness, rmse, iters
 
     def evaluate_p2p(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
@@ -372,10 +395,11 @@ class PoseCore:
                      calc_obs_cost: bool = True, stride: int = 8, depth_factor: float = 100.0,
                      sensor_resolution: float = 0.01, occlusion_threshold: float = 1.0,
                      max_iterations: int = _native.P2P_MAX_ITER, relative_fitness: float = _native.P2P_REL_FITNESS,
-                     relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: float = _native.P2P_MAX_DIST_DIFF,
-                     color_distance_threshold: float = 15.0, stream=None):
+                     relative_rmse: float = _native.P2P_REL_RMSE, max_dist_diff: Optional[float] = None,
+                     color_distance_threshold: float = 15.0, stream=None, scene: str = "projective",
+                     window: int = _native.NN_WINDOW):
         """Stage COST with the point-to-plane ICP in GICP's place: icp_point2plane with out_poses, then evaluate on the
-        adjusted poses.  Returns (adjusted poses (N, 16), iterations (N,), rc, oc, diff, fitness, rmse)."""
+        adjusted poses (scene and window as icp_point2plane).  Returns (adjusted poses (N, 16), iterations (N,), rc, oc, diff, fitness, rmse)."""
         n = int(poses.shape[0])
         adj = torch.empty((n, 16), dtype=torch.float32, device=poses.device)
         label = pose_label if cost_type == _native.COST_DEPTH_6DOF else None
@@ -383,7 +407,7 @@ class PoseCore:
             poses, pose_model, label, cost_type=cost_type, stride=stride, depth_factor=depth_factor,
             occlusion_threshold=occlusion_threshold, max_iterations=max_iterations,
             relative_fitness=relative_fitness, relative_rmse=relative_rmse, max_dist_diff=max_dist_diff,
-            out_poses=adj, stream=stream)
+            out_poses=adj, stream=stream, scene=scene, window=window)
         rc, oc, df = self.evaluate(adj, pose_model, pose_label, pose_obs_total, cost_type=cost_type,
                                    calc_obs_cost=calc_obs_cost, stride=stride, depth_factor=depth_factor,
                                    sensor_resolution=sensor_resolution, occlusion_threshold=occlusion_threshold,

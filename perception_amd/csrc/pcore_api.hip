@@ -1260,30 +1260,71 @@ const char* p2p_params_error(const pcore_p2p_icp_params* ip) {
     return nullptr;
 }
 
+// pcore_nn_icp_params' checks
+const char* nn_params_error(const pcore_nn_icp_params* ip) {
+    if (ip->max_iterations < 0) return "max_iterations must be >= 0";
+    if (std::isnan(ip->relative_fitness) || ip->relative_fitness < 0.0f) return "relative_fitness must be >= 0";
+    if (std::isnan(ip->relative_rmse) || ip->relative_rmse < 0.0f) return "relative_rmse must be >= 0";
+    if (!(ip->max_dist_diff > 0.0f)) return "max_dist_diff must be > 0";
+    if (ip->window < 0 || ip->window > p2p::kNnMaxWindow) return "window must be 0 ... 128";
+    return nullptr;
+}
+
+// the two entry points' common body: nn == nullptr is the projective scene (ip), else the nearest-neighbour one
+int icp_point2plane_impl(pcore_ctx* c, const char* who, const float* d_poses, const int32_t* d_pose_model,
+                         const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* p,
+                         const pcore_p2p_icp_params* ip, const pcore_nn_icp_params* nn, float* d_out_T,
+                         float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, float* d_out_poses,
+                         pcore_stream stream);
+
 }  // namespace
 
-// Point-to-plane ICP against the projective scene of the observation's source depth (ICP_Point2Plane_cuda,
-// cuda_icp/icp.cu:157-218): stage CLOUD into per-pose slots (launch_render_cloud, as pcore_evaluate_icp's first step),
-// then p2p_icp_kernel over the slots.  Every check comes before the first launch, so an invalid call writes nothing.
 int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
                           int32_t num_poses, const pcore_eval_params* p, const pcore_p2p_icp_params* ip,
                           float* d_out_T, float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters,
                           float* d_out_poses, pcore_stream stream) {
     if (!c) return PCORE_E_INVALID_ARG;
     if (!p || !ip) return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: null parameters");
+    return icp_point2plane_impl(c, "icp_point2plane", d_poses, d_pose_model, d_pose_label, num_poses, p, ip, nullptr,
+                                d_out_T, d_out_fitness, d_out_rmse, d_out_iters, d_out_poses, stream);
+}
+
+// The same against the nearest-neighbour scene (Scene_nn, pcd_scene.h:48-137): the scene buffers, their cache and
+// rebuild keys, the scratch budget and the chunking are pcore_icp_point2plane's.
+int pcore_icp_point2plane_nn(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model,
+                             const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* p,
+                             const pcore_nn_icp_params* ip, float* d_out_T, float* d_out_fitness, float* d_out_rmse,
+                             int32_t* d_out_iters, float* d_out_poses, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (!p || !ip) return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane_nn: null parameters");
+    return icp_point2plane_impl(c, "icp_point2plane_nn", d_poses, d_pose_model, d_pose_label, num_poses, p, nullptr, ip,
+                                d_out_T, d_out_fitness, d_out_rmse, d_out_iters, d_out_poses, stream);
+}
+
+namespace {
+
+// Point-to-plane ICP against the projective scene of the observation's source depth (ICP_Point2Plane_cuda,
+// cuda_icp/icp.cu:157-218): stage CLOUD into per-pose slots (launch_render_cloud, as pcore_evaluate_icp's first step),
+// then p2p_icp_kernel over the slots.  Every check comes before the first launch, so an invalid call writes nothing.
+int icp_point2plane_impl(pcore_ctx* c, const char* who, const float* d_poses, const int32_t* d_pose_model,
+                         const int32_t* d_pose_label, int32_t num_poses, const pcore_eval_params* p,
+                         const pcore_p2p_icp_params* ip, const pcore_nn_icp_params* nn, float* d_out_T,
+                         float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, float* d_out_poses,
+                         pcore_stream stream) {
+    const std::string pre = std::string(who) + ": ";
     if (!c->have_mesh || !c->have_cam || !c->have_obs)
-        return fail(c, PCORE_E_STATE, "icp_point2plane: meshes, camera and observation must be set first");
+        return fail(c, PCORE_E_STATE, pre + "meshes, camera and observation must be set first");
     if (p->cost_type != PCORE_COST_DEPTH_3DOF && p->cost_type != PCORE_COST_DEPTH_6DOF &&
         p->cost_type != PCORE_COST_RGBD_3DOF)
-        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: unknown cost_type");
-    if (const char* e = p2p_params_error(ip)) return fail(c, PCORE_E_INVALID_ARG, std::string("icp_point2plane: ") + e);
+        return fail(c, PCORE_E_INVALID_ARG, pre + "unknown cost_type");
+    if (const char* e = nn ? nn_params_error(nn) : p2p_params_error(ip)) return fail(c, PCORE_E_INVALID_ARG, pre + e);
     if (num_poses < 0 || (num_poses > 0 && (!d_poses || !d_pose_model || !d_out_T || !d_out_fitness || !d_out_rmse ||
                                             !d_out_iters)))
-        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: null pose / output pointer");
+        return fail(c, PCORE_E_INVALID_ARG, pre + "null pose / output pointer");
     if (d_pose_label && !c->obs_has_mask)
-        return fail(c, PCORE_E_INVALID_ARG, "icp_point2plane: pose labels need a source mask");
+        return fail(c, PCORE_E_INVALID_ARG, pre + "pose labels need a source mask");
     int ws, hs;
-    if (const int vr = check_sampling(c, "icp_point2plane", p->stride, false, " (use a larger stride)", false, ws, hs))
+    if (const int vr = check_sampling(c, who, p->stride, false, " (use a larger stride)", false, ws, hs))
         return vr;
     if (num_poses == 0) return PCORE_OK;
     HIPC(c, hipSetDevice(c->device));
@@ -1302,7 +1343,7 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
                              std::memcmp(&c->p2p_cam.cy, &cam.cy, sizeof(float)) != 0;
     const bool setup = scene_stale || c->sampled_stride != p->stride || !c->icp_cloud.p || !c->icp_count.p ||
                        c->icp_cloud.n < (size_t)chunk * nsamp || c->icp_count.n < (size_t)chunk;
-    if (const int cr = refuse_setup_in_capture(c, "icp_point2plane", "the scene", setup, s)) return cr;
+    if (const int cr = refuse_setup_in_capture(c, who, "the scene", setup, s)) return cr;
     if (scene_stale) {
         const size_t npx = (size_t)W * H;
         HIPC(c, hipStreamSynchronize(s));  // an earlier call on the stream may still read the old scene
@@ -1330,10 +1371,11 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
     g.width = W;
     g.height = H;
     g.fx = cam.fx; g.fy = cam.fy; g.cx = cam.cx; g.cy = cam.cy;
-    g.max_dist_diff = ip->max_dist_diff;
-    g.rel_fitness = ip->relative_fitness;
-    g.rel_rmse = ip->relative_rmse;
-    g.max_iter = ip->max_iterations;
+    g.max_dist_diff = nn ? nn->max_dist_diff : ip->max_dist_diff;
+    g.rel_fitness = nn ? nn->relative_fitness : ip->relative_fitness;
+    g.rel_rmse = nn ? nn->relative_rmse : ip->relative_rmse;
+    g.max_iter = nn ? nn->max_iterations : ip->max_iterations;
+    g.window = nn ? nn->window : 0;
     g.poses_in = d_poses;
     g.poses_out = d_out_poses;
     g.out_T = d_out_T;
@@ -1345,10 +1387,12 @@ int pcore_icp_point2plane(pcore_ctx* c, const float* d_poses, const int32_t* d_p
         HIPC(c, stage_clouds(c, a, d_poses + (size_t)16 * base, d_pose_model + base,
                              d_pose_label ? d_pose_label + base : nullptr, n, c->icp_cloud.p, c->icp_count.p, s));
         g.pose_base = base;
-        HIPC(c, launch_p2p_icp(g, n, s));
+        HIPC(c, nn ? launch_p2p_nn_icp(g, n, s) : launch_p2p_icp(g, n, s));
     }
     return PCORE_OK;
 }
+
+}  // namespace
 
 int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_t seg_stride, int32_t num_segs,
                            const float* d_scene_pcd4, const float* d_scene_normal4, int32_t width, int32_t height,
@@ -1377,6 +1421,36 @@ int pcore_debug_p2p_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_
     g.out_rmse = d_out_rmse;
     g.out_iters = d_out_iters;
     return launch_p2p_icp(g, num_segs, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
+}
+
+int pcore_debug_p2p_nn_clouds(const float* d_xyzw, const int32_t* d_seg_cnt, int32_t seg_stride, int32_t num_segs,
+                              const float* d_scene_pcd4, const float* d_scene_normal4, int32_t width, int32_t height,
+                              float fx, float fy, float cx, float cy, const pcore_nn_icp_params* ip, float* d_out_T,
+                              float* d_out_fitness, float* d_out_rmse, int32_t* d_out_iters, pcore_stream stream) {
+    if (!ip || nn_params_error(ip) || num_segs < 0 || seg_stride < 0 || width <= 0 || height <= 0 || width > 16384 ||
+        height > 16384 || !d_scene_pcd4 || !d_scene_normal4)
+        return PCORE_E_INVALID_ARG;
+    if (num_segs > 0 && (!d_xyzw || !d_seg_cnt || !d_out_T || !d_out_fitness || !d_out_rmse || !d_out_iters))
+        return PCORE_E_INVALID_ARG;
+    P2pArgs g{};
+    g.src = (float4*)d_xyzw;
+    g.src_count = d_seg_cnt;
+    g.src_cap = seg_stride;
+    g.scene_pcd = (const float4*)d_scene_pcd4;
+    g.scene_normal = (const float4*)d_scene_normal4;
+    g.width = width;
+    g.height = height;
+    g.fx = fx; g.fy = fy; g.cx = cx; g.cy = cy;
+    g.max_dist_diff = ip->max_dist_diff;
+    g.rel_fitness = ip->relative_fitness;
+    g.rel_rmse = ip->relative_rmse;
+    g.max_iter = ip->max_iterations;
+    g.window = ip->window;
+    g.out_T = d_out_T;
+    g.out_fitness = d_out_fitness;
+    g.out_rmse = d_out_rmse;
+    g.out_iters = d_out_iters;
+    return launch_p2p_nn_icp(g, num_segs, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;
 }
 
 // Test hook: stage CLOUD into caller-made slots (render_cloud_kernel as pcore_evaluate_icp, pcore_icp_planar and

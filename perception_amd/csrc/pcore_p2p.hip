@@ -82,6 +82,8 @@ __device__ __forceinline__ void wave_sum(p2p::Sums& S) {
         for (int k = 0; k < p2p::kRow; k++) S.v[k] = S.v[k] + __shfl_xor(S.v[k], m, 64);
 }
 
+// NN: the query of the nearest-neighbour scene (p2p::nn_query) in the projective one's place; nothing else differs.
+template <bool NN>
 __device__ void p2p_pose(const P2pArgs& a, int pose, int lane) {
     float4* slot = a.src + (size_t)pose * a.src_cap;
     int n = __builtin_amdgcn_readfirstlane(a.src_count[pose]);
@@ -101,14 +103,22 @@ __device__ void p2p_pose(const P2pArgs& a, int pose, int lane) {
                 p = make_float4(qx, qy, qz, p.w);
                 slot[i] = p;
             }
-            int x, y;
-            const bool okx = p2p::pixel(p.x, p.z, a.fx, a.cx, x);
-            const bool oky = p2p::pixel(p.y, p.z, a.fy, a.cy, y);
-            const bool in = okx && oky && x >= 0 && x < a.width && y >= 0 && y < a.height;
-            const size_t idx = in ? (size_t)x + (size_t)y * (size_t)a.width : 0;
+            size_t idx;
+            bool in;
+            float d2 = 0.0f;
+            if constexpr (NN) {
+                in = p2p::nn_query(a.scene_pcd, a.width, a.height, a.fx, a.fy, a.cx, a.cy, a.window, a.max_dist_diff,
+                                   p.x, p.y, p.z, idx, d2);
+            } else {
+                int x, y;
+                const bool okx = p2p::pixel(p.x, p.z, a.fx, a.cx, x);
+                const bool oky = p2p::pixel(p.y, p.z, a.fy, a.cy, y);
+                in = okx && oky && x >= 0 && x < a.width && y >= 0 && y < a.height;
+                idx = in ? (size_t)x + (size_t)y * (size_t)a.width : 0;
+            }
             const float4 d = a.scene_pcd[idx];
             const float4 nn = a.scene_normal[idx];
-            const bool ok = in && p2p::accept(p.z, d.z, a.max_dist_diff);
+            const bool ok = in && (NN ? d2 < a.max_dist_diff * a.max_dist_diff : p2p::accept(p.z, d.z, a.max_dist_diff));
             float r[p2p::kRow];
             p2p::row(p.x, p.y, p.z, d.x, d.y, d.z, nn.x, nn.y, nn.z, r);
 #pragma unroll
@@ -168,7 +178,12 @@ __device__ void p2p_pose(const P2pArgs& a, int pose, int lane) {
 
 __global__ void __launch_bounds__(64) p2p_icp_kernel(P2pArgs a, int num_poses) {
     const int pose = blockIdx.x;  // chunk-local
-    if (pose < num_poses) p2p_pose(a, pose, threadIdx.x);
+    if (pose < num_poses) p2p_pose<false>(a, pose, threadIdx.x);
+}
+
+__global__ void __launch_bounds__(64) p2p_icp_nn_kernel(P2pArgs a, int num_poses) {
+    const int pose = blockIdx.x;  // chunk-local
+    if (pose < num_poses) p2p_pose<true>(a, pose, threadIdx.x);
 }
 
 }  // namespace
@@ -176,6 +191,12 @@ __global__ void __launch_bounds__(64) p2p_icp_kernel(P2pArgs a, int num_poses) {
 hipError_t launch_p2p_icp(const P2pArgs& a, int num_poses, hipStream_t s) {
     if (num_poses <= 0) return hipSuccess;
     hipLaunchKernelGGL(p2p_icp_kernel, dim3(num_poses), dim3(64), 0, s, a, num_poses);
+    return hipGetLastError();
+}
+
+hipError_t launch_p2p_nn_icp(const P2pArgs& a, int num_poses, hipStream_t s) {
+    if (num_poses <= 0) return hipSuccess;
+    hipLaunchKernelGGL(p2p_icp_nn_kernel, dim3(num_poses), dim3(64), 0, s, a, num_poses);
     return hipGetLastError();
 }
 

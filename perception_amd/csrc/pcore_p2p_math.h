@@ -67,6 +67,93 @@ PCORE_P2P bool accept(float sz, float dz_scene, float max_dist_diff) {
     return !(dz_scene <= 0 || adz > max_dist_diff);
 }
 
+// The nearest-neighbour scene's query ("Nearest-neighbour scene"; the reference's Scene_nn,
+// pcd_scene.h:48-137, with the kd-tree replaced by an exact search over a pixel window).  Among the pixels (c, q) of
+// the image with |c - x| <= window and |q - y| <= window around the query's own pixel (x, y) whose scene point P has
+// P.z > 0, the one with the smallest d2 = (dx dx + dy dy) + dz dz wins, the lowest index q W + c on equal d2; it is
+// accepted iff d2 < max_dist_diff^2.
+constexpr int kNnMaxWindow = 128;
+constexpr int kNnBatch = 8;  // candidates loaded ahead of the comparisons, per row
+
+// One axis of the rectangle that holds every pixel whose scene point can lie within rho of the query: the scene is
+// dep2pcd of a depth image in centimetres, P.x = fl(fl((c - cx) / fx) P.z) with P.z >= 0.01, so c - cx is P.x / P.z fx
+// to within 2^-21 of its size (0.008 pixel at the largest image) for P.x in [s - rho, s + rho] and P.z in [z_lo, z_hi];
+// x / z takes its extremes at the corners.  The range [lo, hi] (the window clipped to the image) shrinks to the
+// corners' pixels widened by one; a corner that is not a number leaves its side of the window as it is.
+PCORE_P2P void nn_axis_bound(float s, float rho, float z_lo, float z_hi, float f, float c, int& lo, int& hi) {
+    const float a = s - rho, b = s + rho;
+    const float v0 = (a / z_lo) * f + c, v1 = (a / z_hi) * f + c, v2 = (b / z_lo) * f + c, v3 = (b / z_hi) * f + c;
+    const float m01 = v0 < v1 ? v0 : v1, m23 = v2 < v3 ? v2 : v3, M01 = v0 > v1 ? v0 : v1, M23 = v2 > v3 ? v2 : v3;
+    const bool num = v0 == v0 && v1 == v1 && v2 == v2 && v3 == v3;
+    const float vmin = (m01 < m23 ? m01 : m23) - 2.0f;  // floor + 1 pixel: v - 2 < floor(v) - 1
+    const float vmax = (M01 > M23 ? M01 : M23) + 2.0f;
+    if (!num) return;
+    // |lo|, |hi| <= 16384 + 128: exact as floats, and the conversions below are of values between them
+    if (vmin > (float)hi) {
+        lo = hi + 1;
+        return;
+    }
+    if (vmax < (float)lo) {
+        hi = lo - 1;
+        return;
+    }
+    if (vmin > (float)lo) lo = (int)vmin;  // vmin > lo >= 0: truncation is floor
+    if (vmax < (float)hi) hi = (int)vmax + 1;
+    if (hi < lo) hi = lo - 1;
+}
+
+// The winner's pixel index and d2 (found == false: no candidate).  Pcd4 has float members x, y, z.  Every load is at
+// a pixel of the image, whatever s holds; the two loops run over at most (2 window + 1)^2 pixels.
+template <class Pcd4>
+PCORE_P2P bool nn_query(const Pcd4* pcd, int W, int H, float fx, float fy, float cx, float cy, int window, float r,
+                        float sx, float sy, float sz, size_t& best_idx, float& best_d2) {
+    best_idx = 0;
+    best_d2 = 0.0f;
+    int x, y;
+    const bool okx = pixel(sx, sz, fx, cx, x);
+    const bool oky = pixel(sy, sz, fy, cy, y);
+    if (!(okx && oky && sz > 0)) return false;
+    // the window clipped to the image, without forming x +- window where it could overflow
+    if (x < -window || x > W - 1 + window || y < -window || y > H - 1 + window) return false;
+    int c0 = x - window < 0 ? 0 : x - window, c1 = x + window > W - 1 ? W - 1 : x + window;
+    int q0 = y - window < 0 ? 0 : y - window, q1 = y + window > H - 1 ? H - 1 : y + window;
+    // nothing at or beyond r is accepted (d2 < r r needs |dx|, |dy|, |dz| < r (1 + 2^-22)), so only the pixels that
+    // can hold a point within rho = r (1 + 2^-13) need a look; where none of them has a point, no winner is reported,
+    // and the winner of the whole window would have been refused
+    const float rho = r * 1.0001220703125f;
+    const float zl = sz - rho, z_lo = zl > 0.0099f ? zl : 0.0099f, z_hi = sz + rho;
+    nn_axis_bound(sx, rho, z_lo, z_hi, fx, cx, c0, c1);
+    nn_axis_bound(sy, rho, z_lo, z_hi, fy, cy, q0, q1);
+    bool found = false;
+    float best = 0.0f;
+    size_t bi = 0;
+    for (int q = q0; q <= q1; q++) {
+        const size_t base = (size_t)q * (size_t)W;
+        for (int cb = c0; cb <= c1; cb += kNnBatch) {
+            // a batch of independent loads (a lone load per candidate leaves the search waiting on memory), the ones
+            // past the row's end repeated at c1 and skipped below; candidates are still taken in index order
+            Pcd4 P[kNnBatch];
+#pragma unroll
+            for (int k = 0; k < kNnBatch; k++) P[k] = pcd[base + (size_t)(cb + k <= c1 ? cb + k : c1)];
+#pragma unroll
+            for (int k = 0; k < kNnBatch; k++) {
+                const float dx = sx - P[k].x, dy = sy - P[k].y, dz = sz - P[k].z;
+                const float d2 = (dx * dx + dy * dy) + dz * dz;
+                // index order: the first of equals stays
+                const bool better = cb + k <= c1 && P[k].z > 0 && (!found ? d2 == d2 : d2 < best);
+                if (better) {
+                    found = true;
+                    best = d2;
+                    bi = base + (size_t)(cb + k);
+                }
+            }
+        }
+    }
+    best_idx = bi;
+    best_d2 = best;
+    return found;
+}
+
 // thrust__pcd2Ab's row of one accepted pair
 PCORE_P2P void row(float sx, float sy, float sz, float dx, float dy, float dz, float nx, float ny, float nz,
                    float (&r)[kRow]) {
@@ -288,9 +375,12 @@ struct P2pArgs {
     float* out_rmse;
     int32_t* out_iters;
     int32_t pose_base;          // first batch index of this chunk
+    int32_t window;             // the nearest-neighbour scene's half-width in pixels (launch_p2p_nn_icp only)
 };
 // one one-wave workgroup per pose of the chunk
 hipError_t launch_p2p_icp(const P2pArgs& a, int num_poses, hipStream_t s);
+// the same over the nearest-neighbour scene: max_dist_diff is the radius, window the search's half-width
+hipError_t launch_p2p_nn_icp(const P2pArgs& a, int num_poses, hipStream_t s);
 // one thread per pixel: pcd4 / normal4 (float4 per pixel), and / or the packed 3-float buffers; each nullable
 hipError_t launch_p2p_scene(const int32_t* depth_cm, int width, int height, float fx, float fy, float cx, float cy,
                             float4* pcd4, float4* normal4, float* pcd3, float* normal3, hipStream_t s);

@@ -53,6 +53,9 @@ PERCH_PARAM_DEFAULTS = {
     "use_model_specific_search_resolution": ("use_model_specific_search_resolution", False),
     # a build extension (no reference counterpart): the staged search's shortlist per model, 0 = refine every state
     "icp_top_k": ("icp_top_k", 0),
+    # build extensions: the nearest-neighbour scene of icp_type 5 (its radius in metres, its window's half-width in pixels)
+    "nn_max_dist_diff": ("nn_max_dist_diff", 0.01),
+    "nn_window": ("nn_window", 32),
 }
 # object_recognizer.cpp:57-77
 CAMERA_DEFAULTS = {"camera_width": 640, "camera_height": 480, "camera_fx": 576.09757860, "camera_fy": 576.09757860,

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import io as pio
-from ._native import (COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, P2P_MAX_DIST_DIFF, P2P_MAX_ITER,
-                      P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE, PCORE_TOPK_MAX)
+from ._native import (COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, NN_MAX_DIST_DIFF, NN_WINDOW,
+                      P2P_MAX_DIST_DIFF, P2P_MAX_ITER, P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE, PCORE_TOPK_MAX)
 from .core import PoseCore, decode_keys
 from .distributed import allgather_topk_keys, allreduce_min_keys, shard_range
 from .model import (Model, chain_matmul_batch, compute_proj, init_from_eigen_batch, matmul_lazy, pose_matrix_batch,
@@ -43,7 +43,8 @@ class PerchParams:
     """perch_params of sbpl_perception/config/pr3_env_config.yaml (6-DoF GPU settings) + defaults of
     search_env.cpp:153-188."""
     # 3 = GICP inside the GPU flow; 0 = the 3-DoF planar ICP; 4 = point-to-plane projective ICP inside the GPU flow
-    # (a build extension: the reference's icp_type goes to 3; its cuda_icp library has the kernel, PoseCore.evaluate_p2p)
+    # (a build extension: the reference's icp_type goes to 3; its cuda_icp library has the kernel, PoseCore.evaluate_p2p);
+    # 5 = the same loop against the nearest-neighbour scene (cuda_icp's Scene_nn, PoseCore.evaluate_p2p(scene="nn"))
     icp_type: int = 3
     sensor_resolution: float = 0.01          # sensor_resolution_radius (m)
     min_neighbor_points_for_valid_pose: int = 30
@@ -72,7 +73,12 @@ class PerchParams:
     p2p_relative_fitness: float = P2P_REL_FITNESS
     p2p_relative_rmse: float = P2P_REL_RMSE
     p2p_max_dist_diff: float = P2P_MAX_DIST_DIFF
-    # the staged search (a build extension, INTEGRATION.md "Staged search"): with use_icp and icp_type 3 or 4, score
+    # the nearest-neighbour scene of icp_type 5 (pcd_scene.h:49; the search window's half-width in pixels, 0 .. 128);
+    # the loop's criteria are the p2p_ ones above.  The source depth is integer centimetres: the scene is quantised at
+    # the size of the default radius
+    nn_max_dist_diff: float = NN_MAX_DIST_DIFF
+    nn_window: int = NN_WINDOW
+    # the staged search (a build extension, INTEGRATION.md "Staged search"): with use_icp and icp_type 3, 4 or 5, score
     # every state without ICP, refine only the icp_top_k best per model (1 .. 64) and select among the refined;
     # 0 = the reference's flow, every state refined
     icp_top_k: int = 0
@@ -487,8 +493,17 @@ class ObjectRecognizer:
             raise ValueError(f"icp_top_k must lie in [0, {PCORE_TOPK_MAX}], got {k}")
         if p.icp_type == 0:
             raise ValueError("icp_top_k: the planar ICP of icp_type 0 refines the states before they are scored; "
-                             "the staged search needs icp_type 3 or 4")
-        return k if inp.use_icp and p.icp_type in (3, 4) else 0
+                             "the staged search needs icp_type 3, 4 or 5")
+        return k if inp.use_icp and p.icp_type in (3, 4, 5) else 0
+
+    def _p2p_kw(self) -> dict:
+        """evaluate_p2p's ICP arguments for icp_type 4 (the projective scene) or 5 (the nearest-neighbour one)."""
+        p = self.params
+        kw = dict(max_iterations=p.p2p_max_iterations, relative_fitness=p.p2p_relative_fitness,
+                  relative_rmse=p.p2p_relative_rmse, max_dist_diff=p.p2p_max_dist_diff)
+        if p.icp_type == 5:
+            kw.update(max_dist_diff=p.nn_max_dist_diff, window=p.nn_window, scene="nn")
+        return kw
 
     def _staged_refine(self, k: int, lo: int, hi: int, K: int, keys: torch.Tensor, shard):
         """Stages 2 and 3 of the staged search over a shard already scored without ICP: the k best pre-ICP keys per
@@ -512,8 +527,7 @@ class ObjectRecognizer:
             icp_kw = dict(k=p.icp_k, max_iterations=p.icp_max_iterations, rotation_epsilon=p.icp_rotation_epsilon,
                           transformation_epsilon=p.icp_transformation_epsilon)
         else:
-            icp_kw = dict(max_iterations=p.p2p_max_iterations, relative_fitness=p.p2p_relative_fitness,
-                          relative_rmse=p.p2p_relative_rmse, max_dist_diff=p.p2p_max_dist_diff)
+            icp_kw = self._p2p_kw()
         refined = refine_shortlist(self.core, members, poses, pm, pl, tot, p.icp_type, kw, icp_kw)
         if refined is None:  # no shortlist member in this shard: no call, the keys stay empty
             return None
@@ -590,12 +604,11 @@ class ObjectRecognizer:
                                        transformation_epsilon=p.icp_transformation_epsilon,
                                        out=(adj_all, iters, rc, oc, df))
                 self.core.select(rc, oc, pm, K, index_base=lo, keys=keys)
-            elif p.icp_type == 4 and inp.use_icp:
+            elif p.icp_type in (4, 5) and inp.use_icp:
                 adj_all, iters, rc, oc, df, _, _ = self.core.evaluate_p2p(
                     poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride, depth_factor=p.gpu_depth_factor,
                     sensor_resolution=p.sensor_resolution, occlusion_threshold=p.gpu_occlusion_threshold,
-                    max_iterations=p.p2p_max_iterations, relative_fitness=p.p2p_relative_fitness,
-                    relative_rmse=p.p2p_relative_rmse, max_dist_diff=p.p2p_max_dist_diff)
+                    **self._p2p_kw())
                 self.core.select(rc, oc, pm, K, index_base=lo, keys=keys)
             else:  # the argmin keys folded in the scoring launch (pcore_evaluate_select)
                 self.core.evaluate(poses, pm, pl, tot, cost_type=cost_type, stride=p.gpu_stride,

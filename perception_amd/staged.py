@@ -14,7 +14,7 @@ from ._native import PCORE_KEY_NONE
 from .core import PoseCore, decode_keys
 from .distributed import allgather_topk_keys
 
-ICP_GICP, ICP_P2P = 3, 4  # perch_params icp_type
+ICP_GICP, ICP_P2P, ICP_P2P_NN = 3, 4, 5  # perch_params icp_type
 
 
 def shortlist_members(topk, lo: int, hi: int) -> np.ndarray:
@@ -26,7 +26,7 @@ def shortlist_members(topk, lo: int, hi: int) -> np.ndarray:
 def refine_shortlist(core: PoseCore, members: np.ndarray, poses: torch.Tensor, pose_model: torch.Tensor,
                      pose_label: Optional[torch.Tensor], pose_obs_total: torch.Tensor, icp_type: int, eval_kw: dict,
                      icp_kw: dict):
-    """ICP (icp_type 3: evaluate_icp, 4: evaluate_p2p) and re-scoring of the rows `members` of a shard ->
+    """ICP (icp_type 3: evaluate_icp, 4: evaluate_p2p, 5: evaluate_p2p with scene="nn") and re-scoring of the rows `members` of a shard ->
     (sub, adjusted poses, iterations, rc, oc, diff) of those rows, or None when there is none (no call is made).  A
     pose's result does not depend on the batch it is refined in."""
     if len(members) == 0:
@@ -38,8 +38,10 @@ def refine_shortlist(core: PoseCore, members: np.ndarray, poses: torch.Tensor, p
         a, it, r, o, d = core.evaluate_icp(*args, **eval_kw, **icp_kw)
     elif icp_type == ICP_P2P:
         a, it, r, o, d, _, _ = core.evaluate_p2p(*args, **eval_kw, **icp_kw)
+    elif icp_type == ICP_P2P_NN:
+        a, it, r, o, d, _, _ = core.evaluate_p2p(*args, **eval_kw, **{**icp_kw, "scene": "nn"})
     else:
-        raise ValueError(f"the staged search refines with icp_type 3 or 4, got {icp_type}")
+        raise ValueError(f"the staged search refines with icp_type 3, 4 or 5, got {icp_type}")
     return sub, a, it, r, o, d
 
 

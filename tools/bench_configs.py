@@ -8,6 +8,8 @@ multi-GPU configs).  Prints one JSON line per config.  Not the driver's bench (b
       and GICP on the same states (not in the default list: --configs c1_planar)
   c1_p2p  the same 20,000 states: the point-to-plane projective ICP stage beside the planar ICP stage and GICP
   c3_p2p  C3's batch through evaluate_p2p (point-to-plane ICP + re-score) beside evaluate_icp (GICP + re-score)
+  c1_nn   c1_p2p's states through the nearest-neighbour scene's ICP stage beside the projective stage and GICP
+  c3_nn   C3's batch through evaluate_p2p(scene="nn") beside the projective scene and GICP; the staged step at K = 16
   c3_topk  C3's batch through the staged search (evaluate + select_topk + evaluate_icp on the K best per model + select)
       for K = 1, 4, 16, 64 beside the full evaluate_icp + select
   C2  1 mesh, 10k poses, render + score, 640x480
@@ -351,6 +353,103 @@ def run_c3_p2p(per_model=10000, runs=5):
                       "gicp_iters_mean": float(res["gicp"][1].float().mean().item())}), flush=True)
 
 
+def run_c1_nn(nxy=50, stride=4, runs=5):
+    """c1_nn: the point-to-plane ICP against the nearest-neighbour scene (icp_point2plane(scene="nn"), the defaults:
+    radius 0.01 m, window 32) on c1_planar's 20,000 states, beside the projective stage and GICP on the same context
+    -- `runs` alternating runs each after one warm-up, medians and every run."""
+    g = c1_grid(nxy, stride)
+    core, poses, pm, tot, M, n = (g[k] for k in ("core", "poses", "pm", "tot", "M", "n"))
+    out = {"nn": None, "p2p": None}
+
+    def nn():
+        out["nn"] = core.icp_point2plane(poses, pm, None, cost_type=0, stride=stride, out=out["nn"], scene="nn")
+
+    def p2p():
+        out["p2p"] = core.icp_point2plane(poses, pm, None, cost_type=0, stride=stride, out=out["p2p"])
+
+    def gicp():
+        core.evaluate_icp(poses, pm, None, tot, cost_type=0, stride=stride, sensor_resolution=0.0075)
+
+    fns = {"nn": nn, "p2p": p2p, "gicp": gicp}
+    for fn in fns.values():  # warm-up: scratch, the scene, grids, target covariances
+        _once(fn)
+    t = {k: [] for k in fns}
+    gicp_stage = []
+    for _ in range(runs):  # alternating
+        for k, fn in fns.items():
+            t[k].append(_once(fn))
+        gicp_stage.append(float(core.stats()["icp_runtime"]))
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    _, fit, rmse, iters = (x.cpu().numpy() for x in out["nn"])
+    _, pfit, _, piters = (x.cpu().numpy() for x in out["p2p"])
+    print(json.dumps({"config": "c1_nn", "poses": n, "width": g["W"], "height": g["H"], "stride": stride, "runs": runs,
+                      "max_dist_diff": 0.01, "window": 32,
+                      "nn_s": med["nn"], "nn_poses_per_s": n / med["nn"], "p2p_s": med["p2p"],
+                      "gicp_call_s": med["gicp"], "gicp_stage_s": float(np.median(gicp_stage)),
+                      "nn_s_all": t["nn"], "p2p_s_all": t["p2p"], "gicp_call_s_all": t["gicp"],
+                      "nn_iters_mean": float(iters.mean()), "nn_iters_at_cap": int((iters >= 30).sum()),
+                      "nn_fitness_mean": float(fit.mean()), "nn_rmse_mean": float(rmse.mean()),
+                      "p2p_iters_mean": float(piters.mean()), "p2p_fitness_mean": float(pfit.mean())}), flush=True)
+
+
+def run_c3_nn(per_model=10000, runs=5, k=16):
+    """c3_nn: C3's batch (5 objects, 50k 6-DoF poses) through evaluate_p2p(scene="nn") (the defaults: radius 0.01 m,
+    window 32), beside evaluate_p2p (the projective scene) and evaluate_icp (GICP) on the same context, the two
+    point-to-plane stages alone, and the staged search at K = `k` with icp_type 5 -- `runs` alternating runs each
+    after one warm-up, medians and every run."""
+    from perception_amd.staged import ICP_P2P_NN, staged_step
+    w = workloads.build(names=C3_NAMES, poses_per_model=per_model, cam=syn.CAM_640)
+    n = int(w.poses.shape[0])
+    args = (w.poses, w.pose_model, w.pose_label, w.pose_obs_total)
+    res = {}
+
+    def nn():
+        res["nn"] = w.core.evaluate_p2p(*args, stride=w.stride, scene="nn")
+
+    def nn_stage():
+        res["nn_stage"] = w.core.icp_point2plane(*args[:3], stride=w.stride, scene="nn")
+
+    def p2p():
+        res["p2p"] = w.core.evaluate_p2p(*args, stride=w.stride)
+
+    def p2p_stage():
+        res["p2p_stage"] = w.core.icp_point2plane(*args[:3], stride=w.stride)
+
+    def gicp():
+        res["gicp"] = w.core.evaluate_icp(*args, stride=w.stride)
+
+    def staged():
+        res["staged"] = staged_step(w.core, *args, w.num_models, k, icp_type=ICP_P2P_NN, eval_kw=dict(stride=w.stride))
+
+    fns = {"nn": nn, "nn_stage": nn_stage, "p2p": p2p, "p2p_stage": p2p_stage, "gicp": gicp, "staged": staged}
+    for fn in fns.values():
+        _once(fn)
+    t = {name: [] for name in fns}
+    gicp_stage = []
+    for _ in range(runs):  # alternating
+        for name, fn in fns.items():
+            t[name].append(_once(fn))
+            if name == "gicp":
+                gicp_stage.append(float(w.core.stats()["icp_runtime"]))
+    med = {name: float(np.median(v)) for name, v in t.items()}
+    _, fit, rmse, iters = (x.cpu().numpy() for x in res["nn_stage"])
+    _, pfit, _, piters = (x.cpu().numpy() for x in res["p2p_stage"])
+    refined = res["staged"][2]
+    print(json.dumps({"config": "c3_nn", "poses": n, "models": w.num_models, "stride": w.stride, "runs": runs,
+                      "max_dist_diff": 0.01, "window": 32,
+                      "evaluate_nn_s": med["nn"], "evaluate_nn_poses_per_s": n / med["nn"], "nn_stage_s": med["nn_stage"],
+                      "evaluate_p2p_s": med["p2p"], "p2p_stage_s": med["p2p_stage"], "evaluate_icp_s": med["gicp"],
+                      "gicp_stage_s": float(np.median(gicp_stage)),
+                      "staged_k": k, "staged_nn_s": med["staged"],
+                      "staged_poses_refined": 0 if refined is None else int(len(refined[0])),
+                      "evaluate_nn_s_all": t["nn"], "nn_stage_s_all": t["nn_stage"], "evaluate_p2p_s_all": t["p2p"],
+                      "p2p_stage_s_all": t["p2p_stage"], "evaluate_icp_s_all": t["gicp"], "staged_nn_s_all": t["staged"],
+                      "nn_iters_mean": float(iters.mean()), "nn_iters_at_cap": int((iters >= 30).sum()),
+                      "nn_fitness_mean": float(fit.mean()), "nn_rmse_mean": float(rmse.mean()),
+                      "p2p_iters_mean": float(piters.mean()), "p2p_fitness_mean": float(pfit.mean()),
+                      "gicp_iters_mean": float(res["gicp"][1].float().mean().item())}), flush=True)
+
+
 def run_c3_topk(per_model=10000, runs=5, ks=(1, 4, 16, 64)):
     """c3_topk: C3's batch (5 objects, 50k 6-DoF poses) through the staged search (evaluate + select_topk + evaluate_icp
     on the shortlist + select; perception_amd/staged.py) for each K, beside the full evaluate_icp + select on the same
@@ -422,6 +521,10 @@ def main():
         run_c1_p2p(nxy=max(2, int(round(50 * sc ** 0.5))))
     if "c3_p2p" in sel:
         run_c3_p2p(per_model=max(1, int(10000 * sc)))
+    if "c1_nn" in sel:
+        run_c1_nn(nxy=max(2, int(round(50 * sc ** 0.5))))
+    if "c3_nn" in sel:
+        run_c3_nn(per_model=max(1, int(10000 * sc)))
     if "c3_topk" in sel:
         run_c3_topk(per_model=max(1, int(10000 * sc)))
     if "C2" in sel:
