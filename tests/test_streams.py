@@ -2,7 +2,10 @@
 format pcore_upload_meshes builds): every triangle in exactly one slot, each vertex slot naming a ring entry that
 holds that vertex's exact position and was written by one of the last two vertex passes, one pass per flagged step.
 The GPU parity tests catch a broken stream only through wrong depths; these check the builder directly, on the CPU,
-through tools/stream_stats.cpp compiled with g++ (no GPU, no HIP)."""
+through tools/stream_stats.cpp compiled with g++ (no GPU, no HIP).  The GPU counterpart is
+tests/test_gpu_mesh_shapes.py: the kernel's walk of the uploaded streams on the mesh and bank shapes of
+tests/mesh_cases.py (stream counts 1 to 4 and 8, empty models, a hub vertex, NaN / inf vertices), bit for bit against
+the oracle."""
 import ctypes
 import os
 import subprocess

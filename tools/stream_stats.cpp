@@ -109,6 +109,42 @@ extern "C" int stream_check(const float* tri_xyz, int T, int num_streams, int vr
     return 0;
 }
 
+// In how many vertex passes of each stream the position xyz (exact bits) occupies a slot: out[s] for stream s, at
+// most max_streams of them; returns the number of streams (tests/test_mesh_cases.py: a fan's hub is loaded again
+// as passes age out).
+extern "C" int stream_vertex_passes(const float* tri_xyz, int T, int num_streams, int vring, int ref_passes,
+                                    int chunks, const float* xyz, int32_t* out, int max_streams) {
+    struct K { uint32_t x, y, z; bool operator==(const K& o) const { return x == o.x && y == o.y && z == o.z; } };
+    struct H { size_t operator()(const K& k) const { return (size_t)k.x * 73856093u ^ (size_t)k.y * 19349663u ^ (size_t)k.z * 83492791u; } };
+    std::unordered_map<K, int, H> idx;
+    std::vector<int> tv(3 * (size_t)T);
+    std::vector<float> vxyz;
+    for (int t = 0; t < T; t++)
+        for (int k = 0; k < 3; k++) {
+            const float* p = tri_xyz + 9 * (size_t)t + 3 * k;
+            K key;
+            std::memcpy(&key.x, p, 4); std::memcpy(&key.y, p + 1, 4); std::memcpy(&key.z, p + 2, 4);
+            auto it = idx.find(key);
+            int id;
+            if (it == idx.end()) { id = (int)vxyz.size() / 3; idx.emplace(key, id); vxyz.insert(vxyz.end(), p, p + 3); }
+            else id = it->second;
+            tv[3 * (size_t)t + k] = id;
+        }
+    pcore::streams::Built b;
+    pcore::streams::build_model(tv, vxyz, 0, num_streams, vring, ref_passes, b, chunks);
+    const int S = (int)b.streams.size();
+    for (int s = 0; s < S && s < max_streams; s++) {
+        int n = 0;
+        for (int p = b.streams[s].z; p < b.streams[s].w; p++)
+            for (int l = 0; l < 64; l++) {
+                const auto& v = b.sverts[(size_t)p * 64 + l];
+                if (v.w == 1.0f && std::memcmp(&v.x, xyz, 12) == 0) n++;
+            }
+        out[s] = n;
+    }
+    return S;
+}
+
 // LDS bank conflicts of the fused kernel's triangle stage (its three ds_read_b64 gathers of vertex bounds per step,
 // vbd[(slot & 127)], which every step issues for all 64 lanes whatever the pose) under a placement of the ring slots:
 // physical lane of (buffer b, lane l) = mode 0: l; 1: l ^ 16 (b odd); 2: l ^ (8 b); 3: (l + 16 b) mod 64; 4: l ^ (16 b).
