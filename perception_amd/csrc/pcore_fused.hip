@@ -384,15 +384,19 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
             }
             fp.mark(1);
             if (!(dbg & 2)) {
-                // the triangle's clipped window, packed: pos = first sample (kx0 | ky0 << 16), nxy = its size
-                // (nx | ny << 16), nk = nx * ny samples (0: none)
-                uint32_t pos = 0u, nxy = 0u;
-                int nk = 0;
+                // the triangle's clipped window, packed: pos = first sample (kx0 | ky0 << 16), dbits = its size less
+                // one, (nx - 1) | (ny - 1) << 16
+                uint32_t pos = 0u, dbits = 0u;
+                bool nonempty;
+                // bt: the ballot of nonempty; brest: of the lanes that need the general code -- a non-empty window
+                // of more than one sample (d != 0), or a NaN vertex, whose window is not d
+                uint64_t bt, brest;
                 // the vertices' ring slots (9 bits each) and, for the bounds, their pass parity + lane (7 bits);
                 // the slots proper are decoded only where a rare path needs the screen coordinates
                 auto slot_of = [ct](int k) { return (int)((ct >> (9 * k)) & 511u); };
-                // a padding slot names slot 0 three times: its bounds are read (harmless) and nk forced to 0
+                // a padding slot names slot 0 three times: its bounds are read (harmless) and its window counts as empty
                 const bool pad = ct >> 31;
+                bool nan_tri = false;
                 {
                     // bit-field extracts as v_bfe (asm: the compiler turns them back into shift / mask / add, three
                     // instructions per address instead of v_bfe + v_lshl_add)
@@ -403,14 +407,38 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                     short2v lo = __builtin_elementwise_min(__builtin_elementwise_min(as_s2(w0.x), as_s2(w1.x)), as_s2(w2.x));
                     short2v hi = __builtin_elementwise_max(__builtin_elementwise_max(as_s2(w0.y), as_s2(w1.y)), as_s2(w2.y));
                     // (fastdiv poses have finite screen coordinates: no NaN vertex)
-                    const bool nan_tri = !sw.fastdiv && lo.x < 0 && !pad;
+                    if (!sw.fastdiv) nan_tri = lo.x < 0 && !pad;
                     lo = __builtin_elementwise_max(lo, wfirst);
                     hi = __builtin_elementwise_min(hi, wlast);
                     const short2v d = hi - lo;  // (nx - 1, ny - 1), negative where the window is empty
-                    const short2v one = {1, 1};
                     pos = __builtin_bit_cast(uint32_t, lo);
-                    nxy = __builtin_bit_cast(uint32_t, d + one);
-                    const bool nonempty = (__builtin_bit_cast(uint32_t, d) & 0x80008000u) == 0u && !pad;
+                    dbits = __builtin_bit_cast(uint32_t, d);
+                    nonempty = (dbits & 0x80008000u) == 0u && !pad;
+                    // the wave masks are combined from the ballots of the plain compares with scalar instructions
+                    // (a ballot of the combined predicate costs two more VALU instructions)
+                    bt = __ballot((dbits & 0x80008000u) == 0u) & __ballot(!pad);
+                    brest = bt & __ballot(dbits != 0u);
+                    if (!sw.fastdiv) brest |= __ballot(nan_tri);
+                }
+                // One-sample fast path: when no lane of the step needs the general code, every non-empty window is
+                // exactly one sample (d == 0 in both halves) -- as in every step of a mesh whose triangles span less
+                // than the sample stride -- and the record queue below takes the non-empty lanes as they are: qd =
+                // nonempty, the record (ct, pos), with no sample count, size or big-triangle ballot.  A step with any
+                // other lane takes the general code for all its lanes.  The records of a step, their order included,
+                // are the ones the general code alone would queue, so every z-sample, cloud, colour id and cost keeps
+                // its bits; the ring rules are unchanged: an append adds at most 64 records to fewer than 64 pending
+                // and full batches are flushed right after it, and rec_total advances by the step's total before the
+                // next vertex pass reads hist[].  Both kinds of step share the queue and its flush: a second inlined
+                // copy of the flush grew the kernel's code by 13 % and cost time where windows are large.
+                fs.step(lane, brest ? 0ull : bt, brest, ct);
+                // nxy = the window's size (nx | ny << 16), nk = nx * ny samples (0: none); general steps only
+                uint32_t nxy = 0u;
+                int nk = 0;
+                bool qd = nonempty;  // the lanes that queue their first sample
+                uint64_t bq = bt;
+                if (brest) {
+                    const short2v one = {1, 1};
+                    nxy = __builtin_bit_cast(uint32_t, as_s2(dbits) + one);
                     nk = nonempty ? (int)__umul24(nxy & 0xffffu, nxy >> 16) : 0;
                     if (nan_tri) {
                         // NaN screen coordinates: the reference's exact bbox with its NaN-propagating clamps
@@ -431,53 +459,53 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                         pos = (uint32_t)kx0 | ((uint32_t)ky0 << 16);
                         nxy = (uint32_t)nx | ((uint32_t)ny << 16);
                     }
-                }
-                // large triangles: whole-wave cooperative
-                uint64_t big = __ballot(nk > kSmallK);
-                fs.step(lane, big, nk, ct);
-                if (big) {
-                    // the big triangles' screen vertices, read again (rare: not kept in registers through the step)
-                    float2 q0 = make_float2(0.f, 0.f), q1 = q0, q2 = q0;
-                    float z0 = 0.0f, z1 = 0.0f, z2 = 0.0f;
-                    if (nk > kSmallK) {
-                        const int i0 = slot_of(0), i1 = slot_of(1), i2 = slot_of(2);
-                        q0 = vxy[i0];
-                        q1 = vxy[i1];
-                        q2 = vxy[i2];
-                        z0 = vz[i0];
-                        z1 = vz[i1];
-                        z2 = vz[i2];
-                    }
-                    do {
-                        const int j = __ffsll((unsigned long long)big) - 1;
-                        big &= big - 1;
-                        // j is wave-uniform: v_readlane into SGPRs (no LDS round trip)
-                        auto rl = [&](float x) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); };
-                        TriRec rb;
-                        rb.a0 = rl(q0.x); rb.a1 = rl(q0.y);
-                        rb.b0 = rl(q1.x); rb.b1 = rl(q1.y);
-                        rb.c0 = rl(q2.x); rb.c1 = rl(q2.y);
-                        rb.z0 = rl(z0); rb.z1 = rl(z1); rb.z2 = rl(z2);
-                        const uint32_t bpos = (uint32_t)__builtin_amdgcn_readlane((int)pos, j);
-                        const int bkx0 = (int)(bpos & 0xffffu), bky0 = (int)(bpos >> 16);
-                        const int bnx = (int)((uint32_t)__builtin_amdgcn_readlane((int)nxy, j) & 0xffffu);
-                        const int bnk = __builtin_amdgcn_readlane(nk, j);
-                        const uint32_t bid = IDPASS ? (uint32_t)__builtin_amdgcn_readlane((int)cidt, j) : 0u;
-                        // q / bnx without an integer division: the float quotient is within 1e-3 of q / bnx (q / bnx
-                        // is at most the sample rows), so one correction step gives the exact row
-                        const float inv_nx = 1.0f / (float)bnx;
-                        for (int q = lane; q < bnk; q += kWave) {
-                            int iy = (int)(((float)q + 0.5f) * inv_nx), ix = q - iy * bnx;
-                            if (ix < 0) { iy--; ix += bnx; } else if (ix >= bnx) { iy++; ix -= bnx; }
-                            raster_sample<IDPASS, kNoHalf>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid);
+                    // large triangles: whole-wave cooperative
+                    uint64_t big = __ballot(nk > kSmallK);
+                    fs.slow_step(lane, big, nk);
+                    if (big) {
+                        // the big triangles' screen vertices, read again (rare: not kept in registers through the step)
+                        float2 q0 = make_float2(0.f, 0.f), q1 = q0, q2 = q0;
+                        float z0 = 0.0f, z1 = 0.0f, z2 = 0.0f;
+                        if (nk > kSmallK) {
+                            const int i0 = slot_of(0), i1 = slot_of(1), i2 = slot_of(2);
+                            q0 = vxy[i0];
+                            q1 = vxy[i1];
+                            q2 = vxy[i2];
+                            z0 = vz[i0];
+                            z1 = vz[i1];
+                            z2 = vz[i2];
                         }
-                    } while (big);
+                        do {
+                            const int j = __ffsll((unsigned long long)big) - 1;
+                            big &= big - 1;
+                            // j is wave-uniform: v_readlane into SGPRs (no LDS round trip)
+                            auto rl = [&](float x) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), j)); };
+                            TriRec rb;
+                            rb.a0 = rl(q0.x); rb.a1 = rl(q0.y);
+                            rb.b0 = rl(q1.x); rb.b1 = rl(q1.y);
+                            rb.c0 = rl(q2.x); rb.c1 = rl(q2.y);
+                            rb.z0 = rl(z0); rb.z1 = rl(z1); rb.z2 = rl(z2);
+                            const uint32_t bpos = (uint32_t)__builtin_amdgcn_readlane((int)pos, j);
+                            const int bkx0 = (int)(bpos & 0xffffu), bky0 = (int)(bpos >> 16);
+                            const int bnx = (int)((uint32_t)__builtin_amdgcn_readlane((int)nxy, j) & 0xffffu);
+                            const int bnk = __builtin_amdgcn_readlane(nk, j);
+                            const uint32_t bid = IDPASS ? (uint32_t)__builtin_amdgcn_readlane((int)cidt, j) : 0u;
+                            // q / bnx without an integer division: the float quotient is within 1e-3 of q / bnx (q / bnx
+                            // is at most the sample rows), so one correction step gives the exact row
+                            const float inv_nx = 1.0f / (float)bnx;
+                            for (int q = lane; q < bnk; q += kWave) {
+                                int iy = (int)(((float)q + 0.5f) * inv_nx), ix = q - iy * bnx;
+                                if (ix < 0) { iy--; ix += bnx; } else if (ix >= bnx) { iy++; ix -= bnx; }
+                                raster_sample<IDPASS, kNoHalf>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid);
+                            }
+                        } while (big);
+                    }
+                    qd = nk > 0 && nk <= kSmallK;
+                    bq = __ballot(qd);
                 }
                 // small triangles: one record per (triangle, sample) into the wave's record ring -- the first
-                // sample of every queued triangle, then (rare) the second to fourth of those touching more, one
-                // ballot round each; full 64-record batches are flushed after every round (<= 127 pending)
-                const bool qd = nk > 0 && nk <= kSmallK;
-                const uint64_t bq = __ballot(qd);
+                // sample of every queued triangle, then (general steps) the second to fourth of those touching more,
+                // one ballot round each; full 64-record batches are flushed after every round (<= 127 pending)
                 if (qd) {  // the record keeps the whole triangle slot word (the flush reads its 27 slot bits)
                     const int slot = (rec_total + mbcnt64(bq)) & (kRecCap - 1);
                     ring[slot] = make_uint2(ct, pos);
@@ -485,7 +513,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                 }
                 rec_total += __popcll(bq);
                 while (rec_total - rec_done >= kWave) flush(kWave);  // full batches only
-                if (__ballot(qd && nk > 1)) {
+                if (brest && __ballot(qd && nk > 1)) {
                     for (int q = 1; q < kSmallK; q++) {
                         const bool qr = qd && nk > q;
                         const uint64_t br = __ballot(qr);

@@ -46,11 +46,12 @@ struct FProf {
 
 // Counts of the raster's step loop: [0] flush batches, [1] records in them, [2] fragment tests of queued records,
 // [3] partial flushes (stream switch, vertex ring about to be overwritten), [4] big triangles, [5] triangles touching
-// a sample, [6] triangle slots that are not padding, [7] steps, [8] vertex passes.
+// a sample, [6] triangle slots that are not padding, [7] steps, [8] vertex passes, [9] steps that enter the general
+// (more than one sample, NaN vertex) path instead of the one-sample fast path.
 #ifdef PCORE_FLUSH_STATS
-__device__ unsigned long long pcore_flush_stats[9];
+__device__ unsigned long long pcore_flush_stats[10];
 extern "C" int pcore_debug_flush_stats(unsigned long long* host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pcore_flush_stats), sizeof(unsigned long long) * 9);
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(pcore_flush_stats), sizeof(unsigned long long) * 10);
 }
 struct FlushStats {
     static __device__ __forceinline__ void add(int k, unsigned long long v) { atomicAdd(&pcore_flush_stats[k], v); }
@@ -59,13 +60,20 @@ struct FlushStats {
     }
     __device__ __forceinline__ void record() { add(2, 1ull); }
     __device__ __forceinline__ void partial_flush(int lane) { if (lane == 0) add(3, 1ull); }
-    __device__ __forceinline__ void step(int lane, uint64_t big, int nk, uint32_t ct) {
-        const uint64_t btouch = __ballot(nk > 0), blanes = __ballot(!(ct >> 31));
+    __device__ __forceinline__ void step(int lane, uint64_t single, uint64_t rest, uint32_t ct) {
+        const uint64_t blanes = __ballot(!(ct >> 31));
+        if (lane == 0) {
+            add(6, (unsigned long long)__popcll(blanes));
+            add(7, 1ull);
+            if (rest) add(9, 1ull);  // the general path counts the step's touching triangles (slow_step)
+            else add(5, (unsigned long long)__popcll(single));
+        }
+    }
+    __device__ __forceinline__ void slow_step(int lane, uint64_t big, int nk) {
+        const uint64_t btouch = __ballot(nk > 0);
         if (lane == 0) {
             add(4, (unsigned long long)__popcll(big));
             add(5, (unsigned long long)__popcll(btouch));
-            add(6, (unsigned long long)__popcll(blanes));
-            add(7, 1ull);
         }
     }
     __device__ __forceinline__ void vertex_pass(int lane) { if (lane == 0) add(8, 1ull); }
@@ -75,7 +83,8 @@ struct FlushStats {
     __device__ __forceinline__ void batch(int, int) {}
     __device__ __forceinline__ void record() {}
     __device__ __forceinline__ void partial_flush(int) {}
-    __device__ __forceinline__ void step(int, uint64_t, int, uint32_t) {}
+    __device__ __forceinline__ void step(int, uint64_t, uint64_t, uint32_t) {}
+    __device__ __forceinline__ void slow_step(int, uint64_t, int) {}
     __device__ __forceinline__ void vertex_pass(int) {}
 };
 #endif

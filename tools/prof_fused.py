@@ -9,7 +9,7 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from perception_amd import workloads  # noqa: E402
+from perception_amd import synthetic, workloads  # noqa: E402
 
 
 def main():
@@ -20,10 +20,12 @@ def main():
     ap.add_argument("--c3", action="store_true", help="the 5-object C3 scene")
     ap.add_argument("--iters-json", default=None, help="write the GICP iterations of the last call here (--icp)")
     ap.add_argument("--mesh", default="003_cracker_box", help="the single mesh of the C2 workload (e.g. scan_blob)")
+    ap.add_argument("--cam", default="640", choices=("640", "1280"), help="1280: C5/8's 1280 x 720 camera")
     a = ap.parse_args()
     names = ["003_cracker_box", "005_tomato_soup_can", "006_mustard_bottle", "010_potted_meat_can",
              "024_bowl"] if a.c3 else [a.mesh]
-    w = workloads.build(names=names, poses_per_model=a.poses)
+    w = workloads.build(names=names, poses_per_model=a.poses,
+                        cam=synthetic.CAM_1280 if a.cam == "1280" else synthetic.CAM_640)
     n = int(w.poses.shape[0])
     its = None
     for _ in range(a.iters):
