@@ -19,7 +19,7 @@ namespace pcore {
 
 namespace {
 
-// The cell of a world coordinate along one axis: build_grid's float formula (pcore_api.hip), monotone in v.
+// The cell of a world coordinate along one axis: build_grid's float formula (pcore_prep.h), monotone in v.
 __device__ __forceinline__ float cell_coord(float v, float o, float inv_c) { return (v - o) * inv_c; }
 __device__ __forceinline__ int cell_clamp(float f, int n) {
     const int i = (int)floorf(fmaxf(f, 0.0f));

@@ -1,4 +1,4 @@
-// pcore_topk.h -- launcher of pcore_topk.hip (the k smallest select keys per model), for pcore_api.hip.
+// pcore_topk.h -- launcher of pcore_topk.hip (the k smallest select keys per model), for pcore_api.hip (pcore_select_topk).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -12,8 +12,9 @@ The colour family at the end gives three of these geometries a colour per triang
 which triangle colours a sample, and on which side of the CIEDE2000 gate the pair falls, then decide the costs);
 tests/test_gpu_colour.py runs it.
 
-The neighbour grid (build_grid, pcore_api.hip) and the radius box of the query (process_points, pcore_fused.hip) are
+The neighbour grid (build_grid, pcore_prep.h) and the radius box of the query (process_points, pcore_fused.hip) are
 restated here in float32 numpy with the same formulas, because the placements depend on where the float cell faces lie.
+tests/test_prep.py holds the C++ build_grid to build_grid_np on every segment of every case.
 """
 from __future__ import annotations
 

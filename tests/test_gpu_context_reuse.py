@@ -10,8 +10,8 @@ _pcl_counts), directly and bit for bit, never with a fresh context.  tests/test_
 CPU that each kind of state wrongly kept from the previous scene would change these references' results.
 
 Then the state contract (what a setup call invalidates, what is refused until the next one, pcore_generation and
-captured graphs), and an ObjectRecognizer that localises one scene, another with another model set, and the first
-again."""
+captured graphs, the generation across the slots the staged ICPs share, a context's teardown), and an ObjectRecognizer
+that localises one scene, another with another model set, and the first again."""
 import os
 
 import numpy as np
@@ -333,6 +333,61 @@ def test_setup_calls_invalidate_and_refuse():
         _same_costs(out, tuple(w[lo:lo + N_CAP] for w in want), f"fresh capture, poses from {lo}")
     assert (B.pose_model[:2 * N_CAP] == 0).all() and (B.pose_label[:2 * N_CAP] == 0).all()
     core.close()
+
+
+def _staged_call(core, s, t, which, n):
+    """One call of a staged ICP family on the first n poses of the scene (all of model 0 and label 0)."""
+    poses, pm, pl, tot = (t[k][:n].contiguous() for k in ("poses", "pm", "pl", "tot"))
+    if which == "gicp":
+        return core.evaluate_icp(poses, pm, pl, tot, cost_type=2, stride=s.stride, sensor_resolution=s.res)
+    if which == "planar":
+        return core.icp_planar(poses, pm, cc.PLANAR_M[0], stride=s.stride, max_correspondence=cc.PLANAR_R[0])
+    scene = {"point2plane": "projective", "point2plane_nn": "nn"}[which]
+    return core.icp_point2plane(poses, pm, pl, stride=s.stride, scene=scene)
+
+
+@pytest.mark.parametrize("first", ["planar", "point2plane"])
+def test_evaluate_icp_growing_the_shared_slots_changes_the_generation(first):
+    """pcore.h: the generation changes on every reallocation of per-batch scratch.  The staged ICPs share the slots
+    their clouds are rendered into: after a planar (or point-to-plane) call on 2 poses has sized them, pcore_evaluate_icp
+    on 8 poses at the same stride has to grow them -- memory a graph captured of the first call points into -- and the
+    generation must increase; a second identical call reallocates nothing and leaves it as it is."""
+    s = cc.scene("B")
+    t = _tensors(s)
+    core = PoseCore(0)
+    _load(core, s, t, camera=True)
+    _staged_call(core, s, t, first, 2)
+    g0 = core.generation()
+    _staged_call(core, s, t, "gicp", 8)
+    g1 = core.generation()
+    assert g1 > g0
+    _staged_call(core, s, t, "gicp", 8)
+    assert core.generation() == g1
+    core.close()
+
+
+def test_a_closed_context_leaves_nothing_the_next_one_sees():
+    """A context runs an eager evaluate (the window probe), a captured one (the captured launches' own counters) and one
+    call of each staged ICP family on 2 poses, then closes: every owner of device memory, pinned memory and events is
+    destroyed once.  A second context in the same process repeats the sequence to the same bits."""
+    s = cc.scene("B")
+    t = _tensors(s)
+    rounds = []
+    for _ in range(2):
+        core = PoseCore(0)
+        _load(core, s, t, camera=True)
+        got = list(_evaluate(core, s, t, 2))
+        assert core.tile_info()["tcap"] > 0  # reads the mapped feedback buffer of the launch
+        replay, out = _capture(core, s, t)
+        got += list(out)
+        for which in ("gicp", "planar", "point2plane", "point2plane_nn"):
+            got += list(_staged_call(core, s, t, which, 2))
+        torch.cuda.synchronize()
+        rounds.append([g.cpu().numpy().tobytes() for g in got])
+        del replay
+        core.close()
+    _same_costs([np.frombuffer(b, np.float32) for b in rounds[0][:3]], cc.want_costs("B", 2), "first round")
+    assert len(rounds[0]) == 3 + 3 + 5 + 4 + 4 + 4 and rounds[0] == rounds[1]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -275,7 +275,7 @@ def test_window_tiles_any_tier(one_object, tier, monkeypatch):
 
 
 def _choose_tier(hist, edge):
-    """set_fused_tiles' choose_tier (pcore_api.hip): the first tier whose tile holds >= 99 % of the windows."""
+    """set_fused_tiles' choose_tier (pcore_api_eval.hip): the first tier whose tile holds >= 99 % of the windows."""
     tot = sum(hist)
     over = tot
     for t, e in enumerate(edge):
