@@ -4,13 +4,16 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this
 product package (perception_amd) never imports, links or calls it.
 
 This is a literal restatement of the reference's CUDA/host code (file:line citations in
-pcore_oracle.cpp).  Parity against the reference *binary* is unpinned: the reference path cannot be
-built here and holds no golden vectors for this path ("Oracle").
+pcore_oracle.cpp).  The whole reference path cannot be built here, but its stage kernels can, for the host
+(oracle/ref_host/, build_ref()): tests/golden/refk_*.npz are their outputs, and tests/test_reference_goldens.py holds
+the raster, cloud and cost restatements to them bit for bit ("Oracle").  The pin is to the reference's source
+under this oracle's float flags, not to an nvcc binary.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import shutil
 import subprocess
 
 import numpy as np
@@ -29,6 +32,32 @@ def build() -> str:
     """Compile oracle/build/liboracle.so with the oracle's Makefile (g++, no FMA contraction)."""
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
     return _LIB_PATH
+
+
+def build_ref(reference_root=None) -> str:
+    """Compile the reference's own stage kernels for the host (oracle/ref_host/): oracle/_ref/ref_host, and
+    oracle/_ref/ref_host_san with -fsanitize=address,undefined, both stand-alone programs that are never loaded into
+    Python.  The reference root is PCORE_REFERENCE_ROOT (default /root/reference).  Not part of
+    __graft_entry__.build(): the reference exists only where the goldens are made.  Returns oracle/_ref."""
+    from . import ref_host
+    from .ref_host import filter_sources
+    root = reference_root or ref_host.reference_root()
+    out = ref_host.REF_DIR
+    src = os.path.join(out, "src")
+    filter_sources.filter_sources(root, src)
+    rh = os.path.join(_HERE, "ref_host")
+    # clang++ (ROCm ships one): compute_costs.cuh:167 declares a `const const float`, which g++ rejects even with
+    # -fpermissive and clang only warns about.  The float flags are the oracle's.
+    cxx = os.environ.get("PCORE_REF_CXX") or shutil.which("clang++") or os.path.join(
+        os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
+    base = [cxx, "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
+            "-fno-unsafe-math-optimizations", "-mno-fma", "-w", "-include",
+            os.path.join(rh, "shim", "ref_shim.h"), "-I", os.path.join(rh, "shim"), "-I", src,
+            os.path.join(rh, "driver.cpp")]
+    subprocess.run(base + ["-O2", "-o", os.path.join(out, "ref_host")], check=True)
+    subprocess.run(base + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-o", os.path.join(out, "ref_host_san")], check=True)
+    return out
 
 
 def _opt(ptype):

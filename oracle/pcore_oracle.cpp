@@ -1,5 +1,5 @@
 // pcore_oracle.cpp -- CPU restatement of the reference hot path.  TEST INFRASTRUCTURE ONLY.
-// See pcore_oracle.h for the parity status ("parity unpinned" vs the reference binary).
+// See pcore_oracle.h for the parity status (raster, clouds and costs held to the reference's stage kernels run on the host).
 // Build: oracle/Makefile (g++ -O2 -ffp-contract=off -fno-fast-math -fopenmp).
 #include "pcore_oracle.h"
 

@@ -8,9 +8,12 @@
  * Parity status (see DESIGN.md "Oracle"):
  *   - The reference's own path (CUDA + Thrust + Eigen + assimp + OpenCV + fast_gicp) cannot be
  *     built in this image (no nvcc, no Eigen/OpenCV/assimp headers, fast_gicp not vendored), and
- *     the reference holds no golden vectors for this path.  The raster,
- *     unprojection, cost and selection restatements are therefore pinned only by analytic
- *     known-answer tests: "parity unpinned" against the reference binary.
+ *     the reference holds no golden vectors for this path.  Its stage kernels
+ *     (image_renderer.cuh, compute_point_clouds.cuh, compute_costs.cuh) do compile for the host: oracle/ref_host/
+ *     runs them serially, tests/golden/refk_*.npz are their outputs, and the raster, unprojection and cost
+ *     restatements are held to them bit for bit (tests/test_reference_goldens.py).  That pins the reference's
+ *     source under this file's float flags; nvcc's FMA contraction and conversions stay a reading.  The
+ *     selection is pinned by analytic known-answer tests only.
  *   - KNN tie-break and GICP arithmetic live in the un-vendored fast_gicp fork: build-owned spec,
  *     parity unpinned.
  *

@@ -1,5 +1,6 @@
 """Analytic known-answer tests of the CPU oracle (SURVEY.md 8c "Known-answer tests").  These pin the
-restatement where no reference golden vector exists (parity vs the reference binary is unpinned)."""
+restatement by reasoning alone; tests/test_reference_goldens.py holds the raster, the clouds and the costs to the
+reference's own stage kernels run on the host, and the selection is pinned only here."""
 import numpy as np
 import pytest
 

@@ -1,6 +1,7 @@
 """the reference's CPU/OMP path (render_cpu -> depth2cloud_cpu -> ICP_Point2Plane_cpu
 with Scene_projective), restated in oracle/ref_cpu_path.cpp.  Known answers and cross-checks against the
-oracle's GPU-path restatement; parity against the reference binary is unpinned (Eigen / OpenCV absent)."""
+oracle's GPU-path restatement (which tests/test_reference_goldens.py holds to the reference's own stage kernels); the
+parity of this CPU path itself against the reference binary stays unpinned (it needs Eigen and OpenCV in earnest)."""
 import math
 
 import numpy as np
