@@ -1,7 +1,8 @@
 // pcore_cov.h -- the GICP covariances of a point segment (fast_gicp's k-NN covariances with PLANE regularisation;
 // DESIGN.md section 5): one wave per round of 64 query points, brute-force k-NN over the segment with candidates
 // staged through a 64-point LDS tile, double mean / covariance in list order, Jacobi (<= 6 thresholded sweeps), PLANE regularisation.
-// Used by covariance_kernel and covariance_cloud_kernel (pcore_gicp.hip: one wave per segment).
+// Used by covariance_kernel and covariance_cloud_kernel (pcore_gicp.hip: one wave per segment); the wave primitives are
+// pcore_wave.h's, the point distance pcore_nn_grid.h's.
 // Bit-identical to the oracle's covariance_one (tests/test_gpu_covariances.py, the GICP parity tests).
 #pragma once
 
@@ -10,24 +11,15 @@
 #include <climits>
 #include <type_traits>
 
+#include "pcore_nn_grid.h"
+#include "pcore_wave.h"
+
 namespace pcore {
 namespace {
 
 constexpr double kPlaneScale = 1.0 - 1e-3;
 constexpr double kJacobiEps2 = 4.440892098500626e-16;    // 2 eps (double)
 constexpr double kJacobiTiny = 2.2250738585072014e-308;  // the smallest normal double (Eigen's considerAsZero)
-
-// LDS writes by some lanes of a wave visible to all its lanes (no block barrier: waves are independent)
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return dx * dx + dy * dy + dz * dz;
-}
 
 // Jacobi (at most 6 cyclic sweeps) + PLANE regularisation, same operation order as orc plane_regularize.  A rotation
 // is skipped when its off-diagonal entry is at most 2 eps times the largest diagonal magnitude (Eigen JacobiSVD's
@@ -265,17 +257,6 @@ constexpr size_t kThrLdsBytes = kThrMap * 2 + (size_t)kThrCap * kCovLanes * 2 + 
 __device__ __forceinline__ void cov_cell(const float4& p, const CovGrid& cg, int& kx, int& ky) {
     kx = (int)rintf((p.x / p.z * cg.fx + cg.cx) / (float)cg.stride);
     ky = (int)rintf((p.y / p.z * cg.fy + cg.cy) / (float)cg.stride);
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
 }
 
 // the cloud's window and its cell map (ushort point index per cell); false: the brute force serves this segment

@@ -17,11 +17,24 @@
 //                      damped solve by 3x3 block elimination, se3_exp, the trial), the correspondence history, then
 //                      concatenate_transforms (renderer.cu:1412-1429).
 //   gicp_wide_kernel   small batches: eight waves search a pose's correspondences, wave 0 as gicp_kernel.
+//
+// Here: the kernels, the per-pose state they iterate on and the launchers.  What they are built from lies beside it:
+//   pcore_wave.h        wave primitives: wave_lds_sync, opaque_zero, uniform_d / uniform_f, wave_tree_sums, wave_sum_lane0
+//   pcore_nn_grid.h     the exact grid-shell neighbour search: grid_shells, grid_nn, knn_insert_lex, sqdist3
+//   pcore_gicp_scan.h   the scalar-cache key scan: scan_quads, scan_quads2 (PCORE_SCAN_UNROLL, PCORE_SCAN2_UNROLL)
+//   pcore_gicp_ring.h   float transforms as bit patterns in LDS rings: xform_float, xf_lane_words, ring_match16, CycleExit
+//   pcore_gicp_probe.h  the measurement builds: GPROF_* (PCORE_GICP_PROFILE), GTL_* (PCORE_GICP_TIMELINE)
+// and pcore_cov.h (the covariances' k-NN rounds), pcore_gicp_math.h (the arithmetic shared with the oracle).
 #include "pcore_internal.h"
 
 #include <hipcub/hipcub.hpp>
 #include "pcore_cov.h"
 #include "pcore_gicp_math.h"
+#include "pcore_gicp_probe.h"
+#include "pcore_gicp_ring.h"
+#include "pcore_gicp_scan.h"
+#include "pcore_nn_grid.h"
+#include "pcore_wave.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -36,176 +49,14 @@ namespace {
 
 constexpr int kGThreads = 256;
 constexpr int kMaxK = 16;
-// Build with -DPCORE_GICP_PROFILE to accumulate per-phase shader clocks of gicp_kernel (tools only):
-// [0] correspondence search, [1] contributions (+ M stores), [2] wave reduction, [3] LM iteration, which splits into [4] damped
-// solves, [5] se3_exp + compose, [6] the trials' error sums and their reduction, [7] the decisions; [8] counts the
-// iterations that reused a set of the correspondence history instead of searching.
-// Each wave sums its clocks in registers and adds them once at exit (no atomics inside the loop); each
-// clock read is ordered after its phase's last result by an asm input dependency.
-#ifdef PCORE_GICP_PROFILE
-constexpr int kGprof = 10;  // [9]: the pose-iterations the sums cover (poses of >= PCORE_GICP_PROF_MIN_NS points)
-#ifndef PCORE_GICP_PROF_MIN_NS
-#define PCORE_GICP_PROF_MIN_NS 0
-#endif
-__device__ unsigned long long g_gicp_prof[kGprof];
-#define GPROF_DECL unsigned long long gp_acc[kGprof] = {}
-#define GPROF_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define GPROF_TD(v, dep)                                                                   \
-    unsigned long long v;                                                                  \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "v"(dep) : "memory")
-#define GPROF_ADD(k, a, b) gp_acc[k] += (unsigned long long)((b) - (a))
-#define GPROF_FLUSH \
-    if (lane == 0)  \
-        for (int k_ = 0; k_ < kGprof; k_++) atomicAdd(&g_gicp_prof[k_], gp_acc[k_])
-#define GPROF_PARAM , unsigned long long (&gp_acc)[kGprof]
-#define GPROF_ARG , gp_acc
-#else
-#define GPROF_DECL
-#define GPROF_T(v)
-#define GPROF_TD(v, dep)
-#define GPROF_ADD(k, a, b)
-#define GPROF_FLUSH
-#define GPROF_PARAM
-#define GPROF_ARG
-#endif
-// Build with -DPCORE_GICP_TIMELINE (tools only, tools/gicp_timeline.py): gicp_kernel records, per pose, the real-time
-// clock (100 MHz) when a wave dequeues it and when it writes the refined pose, and per wave its start and exit.
-#ifdef PCORE_GICP_TIMELINE
-constexpr int kTlPoses = 1 << 17, kTlWaves = 1 << 14;
-__device__ unsigned long long g_tl_pose[2 * kTlPoses];
-__device__ unsigned long long g_tl_wave[2 * kTlWaves];
-__device__ unsigned int g_tl_nwaves;
-__device__ int g_tl_run[kTlPoses];  // iterations each pose executed (fewer than it reports after a cycle exit)
-extern "C" int pcore_debug_gicp_timeline_run(int* run) {
-    return hipMemcpyFromSymbol(run, HIP_SYMBOL(g_tl_run), sizeof(g_tl_run)) == hipSuccess ? 0 : 1;
-}
-extern "C" int pcore_debug_gicp_timeline(unsigned long long* poses, unsigned long long* waves, unsigned int* nwaves) {
-    hipError_t e = hipMemcpyFromSymbol(poses, HIP_SYMBOL(g_tl_pose), sizeof(g_tl_pose));
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(waves, HIP_SYMBOL(g_tl_wave), sizeof(g_tl_wave));
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(nwaves, HIP_SYMBOL(g_tl_nwaves), sizeof(unsigned int));
-    const unsigned int z = 0;
-    if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_tl_nwaves), &z, sizeof(z));
-    return e == hipSuccess ? 0 : 1;
-}
-#endif
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 // se3_exp's series coefficients as the kernels read them: an LDS copy through an address-space-3 pointer offset by an
 // opaque zero produced inside the iteration loop, so the loads cannot be hoisted out of it (as literal constants they
 // were hoisted into 64 VGPRs for the whole kernel; a generic pointer made them flat loads) but can be issued together
 // ahead of the series (a volatile pointer serialised them: one LDS round trip per coefficient, 32 in a row)
 typedef __attribute__((address_space(3))) const double lds_cvd;
-__device__ __forceinline__ int opaque_zero() {
-    int z;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-    return z;
-}
 
 }  // namespace
-
-// ------------------------------------------------------------------------------------------------
-// Exact neighbour search over a segment's grid (segments above kGridNNMin points)
-// ------------------------------------------------------------------------------------------------
-//
-// Cells are visited in shells of growing Chebyshev radius r around the query's cell.  A point binned in
-// cell i has its float cell coordinate fp in [i, i + 1) (the grid spans the points' own bounds, so no
-// clamping), so along each axis |fp - fq| is at least the gap between fq and that interval, and the true
-// distance at least (gap - eps) * cell; a cell whose bound exceeds the caller's limit (the best distance,
-// or the k-th best once k are held) is skipped without loading it, and the search stops once the limit is
-// below the bound of the nearest face of the visited box that still has cells beyond it.  Every skipped
-// point is strictly farther than the limit, so the result equals the brute-force scan's lexicographic
-// minimum of (float distance, index).
-// Returns false when the cell budget runs out first (or the query is far outside the grid): the caller
-// then scans the whole segment.  Non-finite queries are the caller's business.
-// Cell budget of one search: a visited cell costs about as much as two points of the in-order scan (its lower-bound
-// test, the CSR range loads, the loop), so the shells may visit up to half the segment's point count before the scan
-// would have been cheaper, and at least 343 cells (r <= 3 around an in-grid query).  C1 (a 19.2 k-point whole-scene
-// target, `tools/c1_gicp_stats.py`): a fixed 343-cell budget sent the queries of poses that GICP walks away from the
-// scene into the 19.2 k-point scan, 64.7 ms per GICP call; budgets of 2,197 / 9,261 / 35,937 cells gave 18.6 / 18.4 /
-// 18.2 ms, and this rule 19.7 ms (profiles/r03x/).  Measured and dropped: the 343-cell shells followed by an exact
-// search over the grid's list of non-empty cells (an upper bound from the least farthest-corner distance, then the
-// cells whose lower bound is within it) instead of the in-order scan, 37.1 ms.
-__device__ __forceinline__ int shell_budget(int n) { return max(343, n >> 1); }
-
-template <typename Visit, typename Limit>
-__device__ __forceinline__ bool grid_shells(const LabelGrid& g, const int32_t* cell_start, float qx, float qy,
-                                            float qz, int budget, Visit&& visit, Limit&& limit) {
-    const float fx = (qx - g.ox) * g.inv_c, fy = (qy - g.oy) * g.inv_c, fz = (qz - g.oz) * g.inv_c;
-    const float fm = fmaxf(fabsf(fx), fmaxf(fabsf(fy), fabsf(fz)));
-    if (!(fm < 65536.0f)) return false;
-    const int cx = (int)floorf(fx), cy = (int)floorf(fy), cz = (int)floorf(fz);
-    const float e = 0.01f + 1e-6f * fm;  // cell-unit slack for the rounding of fp, fq and inv_c
-    const float c2 = g.cell * g.cell * 0.99999f;
-    // lower bound of the float squared distance from q to any point binned in cell (ix, iy, iz): a point's
-    // cell coordinate fp lies in [i, i + 1), so |fp - fq| >= gap along each axis
-    auto cell_lb = [&](int ix, int iy, int iz) {
-        const float gx = fmaxf(fmaxf((float)ix - fx, fx - (float)(ix + 1)) - e, 0.0f);
-        const float gy = fmaxf(fmaxf((float)iy - fy, fy - (float)(iy + 1)) - e, 0.0f);
-        const float gz = fmaxf(fmaxf((float)iz - fz, fz - (float)(iz + 1)) - e, 0.0f);
-        return (gx * gx + gy * gy + gz * gz) * c2;
-    };
-    auto try_cell = [&](int row, int ix, int iy, int iz) {
-        if (cell_lb(ix, iy, iz) > limit()) return;  // every point of the cell is strictly farther
-        visit(cell_start[row + ix], cell_start[row + ix + 1]);
-    };
-    int visited = 0;
-    for (int r = 0;; r++) {
-        const int z0 = max(0, cz - r), z1 = min(g.nz - 1, cz + r);
-        const int y0 = max(0, cy - r), y1 = min(g.ny - 1, cy + r);
-        const int x0 = max(0, cx - r), x1 = min(g.nx - 1, cx + r);
-        for (int iz = z0; iz <= z1; iz++)
-            for (int iy = y0; iy <= y1; iy++) {
-                const int row = g.cell_base + (iz * g.ny + iy) * g.nx;
-                const bool face = iz == cz - r || iz == cz + r || iy == cy - r || iy == cy + r;
-                if (face) {
-                    for (int ix = x0; ix <= x1; ix++) try_cell(row, ix, iy, iz);
-                    visited += x1 >= x0 ? x1 - x0 + 1 : 0;
-                } else {
-                    if (cx - r >= 0 && cx - r < g.nx) {
-                        try_cell(row, cx - r, iy, iz);
-                        visited++;
-                    }
-                    if (r > 0 && cx + r >= 0 && cx + r < g.nx) {
-                        try_cell(row, cx + r, iy, iz);
-                        visited++;
-                    }
-                }
-            }
-        // unvisited cells lie beyond the faces of the box [c - r, c + r + 1) that are inside the grid; the
-        // distance from fq to the nearest such face bounds every unvisited point
-        float B = INFINITY;
-        if (cx - r > 0) B = fminf(B, fx - (float)(cx - r));
-        if (cx + r < g.nx - 1) B = fminf(B, (float)(cx + r + 1) - fx);
-        if (cy - r > 0) B = fminf(B, fy - (float)(cy - r));
-        if (cy + r < g.ny - 1) B = fminf(B, (float)(cy + r + 1) - fy);
-        if (cz - r > 0) B = fminf(B, fz - (float)(cz - r));
-        if (cz + r < g.nz - 1) B = fminf(B, (float)(cz + r + 1) - fz);
-        if (B == INFINITY) return true;  // every cell visited
-        B -= e;
-        if (B > 0.0f && limit() < B * B * c2) return true;
-        if (visited >= budget) return false;
-    }
-}
-
-// k best (distance, index) pairs in lexicographic order, as the brute-force insertion keeps them
-template <int KMAX>
-__device__ __forceinline__ void knn_insert_lex(float (&nd)[KMAX], int (&nb)[KMAX], int& cnt, int k, float d, int j) {
-    if (cnt == k && !(d < nd[k - 1] || (d == nd[k - 1] && j < nb[k - 1]))) return;
-    const int pos = cnt < k ? cnt : k - 1;
-    int c = 0;
-#pragma unroll
-    for (int q = 0; q < KMAX; q++) c += (q < pos && (nd[q] > d || (nd[q] == d && nb[q] > j))) ? 1 : 0;
-    const int fin = pos - c;
-#pragma unroll
-    for (int q = KMAX - 1; q >= 1; q--)
-        if (q > fin && q <= pos) { nd[q] = nd[q - 1]; nb[q] = nb[q - 1]; }
-#pragma unroll
-    for (int q = 0; q < KMAX; q++)
-        if (q == fin) { nd[q] = d; nb[q] = j; }
-    if (cnt < k) cnt++;
-}
 
 // ------------------------------------------------------------------------------------------------
 // covariances
@@ -354,290 +205,10 @@ hipError_t launch_covariances_grid(const float4* pts, const int32_t* seg_off_hos
 // GICP
 // ------------------------------------------------------------------------------------------------
 
-// Nearest target by the segment's grid (segments above kGridNNMin): the lexicographic minimum of (float
-// squared distance, index) -- the brute-force scan's first strict minimum -- or j = -1 when no distance is
-// below +inf (a non-finite query).  Falls back to an in-order scan of the segment.
-__device__ __forceinline__ void grid_nn(const LabelGrid& G, const int32_t* cell_start, const float4* gpts,
-                                        const float4* tgt, int nt, float qx, float qy, float qz, float& best, int& j) {
-    best = INFINITY;
-    j = -1;
-    if (!(isfinite(qx) && isfinite(qy) && isfinite(qz))) return;
-    auto visit = [&](int b, int e) {
-        for (int pi = b; pi < e; pi++) {
-            const float4 o = gpts[pi];
-            const float d = sqdist3(qx, qy, qz, o.x, o.y, o.z);
-            const int oi = __float_as_int(o.w);
-            if (d < best || (d == best && j >= 0 && oi < j)) { best = d; j = oi; }
-        }
-    };
-    if (grid_shells(G, cell_start, qx, qy, qz, shell_budget(nt), visit, [&] { return best; })) return;
-    best = INFINITY;
-    j = -1;
-    for (int i = 0; i < nt; i++) {
-        const float4 o = tgt[i];
-        const float d = sqdist3(qx, qy, qz, o.x, o.y, o.z);
-        if (d < best) { best = d; j = i; }
-    }
-}
-
-// Nearest of a segment's targets read through the scalar cache: every lane scans the same quads of four targets
-// stored as correspondence keys (pcore_gicp_math.h: -2 t'x [4], -2 t'y [4], -2 t'z [4], |t'|^2 [4] about the
-// segment's origin, which the header quad before them holds), so the loads are wave-uniform s_loads and the
-// targets reach the VALU as SGPR operands -- no LDS traffic (an LDS broadcast read still moves 64 lanes x 16 B
-// through the LDS pipe).  A pair of targets costs three packed FMAs.  The index work stays out of the per-quad
-// loop: alternate quads feed two chains that keep only their smallest quad minimum and the first quad reaching it
-// (strict <); the chains merge by (key, quad), and the winning quad's element is found once at the end by
-// recomputing its four keys (the same FMAs, so one of them equals the minimum bit for bit) and taking the first
-// equal one -- the lexicographic minimum of (key, index), i.e. the oracle's first strict minimum.  Measured on
-// C3's GICP call: a per-quad (distance, index) tournament over x / y / z quads 21.9 ms, the index-free scan of
-// float squared distances 21.2 ms.  Keys of finite targets and a finite query are finite, so minNum's NaN
-// handling never decides a comparison.
-typedef __attribute__((address_space(4))) const f4v cf4v;
-#ifndef PCORE_SCAN_UNROLL
-#define PCORE_SCAN_UNROLL 4  // quad pairs per loop trip (C3: 2 -> 4: 20.60 -> 20.45 ms per step; 1: 21.25)
-#endif
-#ifndef PCORE_GICP_PAIR_SCAN
-#define PCORE_GICP_PAIR_SCAN 1  // 0: scan a round pair's queries one after the other (A/B)
-#endif
-#ifndef PCORE_SCAN2_UNROLL
-#define PCORE_SCAN2_UNROLL 2  // scan_quads2: quad pairs per loop trip
-#endif
-
-__device__ __forceinline__ void scan_quads(const float* seg_quads, int nt, float qx, float qy, float qz, float& best,
-                                           int& j) {
-    const int nq = (nt + 3) >> 2;
-    const cf4v* hq = (const cf4v*)seg_quads;
-    const f4v org = hq[0];
-    qx = qx - org.x;
-    qy = qy - org.y;
-    qz = qz - org.z;
-    if (!(__builtin_isfinite(qx) && __builtin_isfinite(qy) && __builtin_isfinite(qz))) return;  // no correspondence
-    const cf4v* tq = hq + 4;
-    const f2v qx2 = {qx, qx}, qy2 = {qy, qy}, qz2 = {qz, qz};
-    float bA = INFINITY, bB = INFINITY;
-    int oA = -1, oB = -1;
-    auto qmin = [&](const cf4v* q) {
-        const f4v X = q[0], Y = q[1], Z = q[2], T = q[3];
-        const f2v ka = __builtin_elementwise_fma(X.xy, qx2, __builtin_elementwise_fma(Y.xy, qy2,
-                                                  __builtin_elementwise_fma(Z.xy, qz2, T.xy)));
-        const f2v kb = __builtin_elementwise_fma(X.zw, qx2, __builtin_elementwise_fma(Y.zw, qy2,
-                                                  __builtin_elementwise_fma(Z.zw, qz2, T.zw)));
-        return fminf(fminf(fminf(ka.x, ka.y), kb.x), kb.y);
-    };
-    int o = 0;
-    const cf4v* q = tq;  // wave-uniform: the quads' addresses stay scalar
-#pragma unroll PCORE_SCAN_UNROLL
-    for (; o + 2 <= nq; o += 2, q += 8) {
-        const float ma = qmin(q);
-        if (ma < bA) { bA = ma; oA = o; }
-        const float mb = qmin(q + 4);
-        if (mb < bB) { bB = mb; oB = o + 1; }
-    }
-    if (o < nq) {
-        const float ma = qmin(q);
-        if (ma < bA) { bA = ma; oA = o; }
-    }
-    if (bB < bA || (bB == bA && oB >= 0 && oB < oA)) { bA = bB; oA = oB; }
-    if (bA < best) {
-        // the winning quad, per lane (a vector load), its first element at the minimum
-        const float* Q = seg_quads + 16 + 16 * oA;
-        const float4 X = *reinterpret_cast<const float4*>(Q), Y = *reinterpret_cast<const float4*>(Q + 4);
-        const float4 Z = *reinterpret_cast<const float4*>(Q + 8), T = *reinterpret_cast<const float4*>(Q + 12);
-        const int k = gicpm::nn_key(X.x, Y.x, Z.x, T.x, qx, qy, qz) == bA ? 0
-                    : gicpm::nn_key(X.y, Y.y, Z.y, T.y, qx, qy, qz) == bA ? 1
-                    : gicpm::nn_key(X.z, Y.z, Z.z, T.z, qx, qy, qz) == bA ? 2 : 3;
-        best = bA;
-        // one of the four recomputed keys equals bA (same FMAs); the clamp only keeps a broken match (which would
-        // pick slot 3, padding in a segment's last quad) inside the segment
-        j = min(4 * oA + k, nt - 1);
-    }
-}
-
-// scan_quads for two queries per lane (the pose's source points i and i + 64): every scalar load of a quad feeds both,
-// so a pair of rounds reads the segment's key quads once.  Each query keeps its own two chains (alternate quads) and
-// its own winner recovery, so (best, j) of each is scan_quads' bit for bit.
-__device__ __forceinline__ void scan_quads2(const float* seg_quads, int nt, float ax, float ay, float az, float bx,
-                                            float by, float bz, int& ja, int& jb) {
-    const int nq = (nt + 3) >> 2;
-    const cf4v* hq = (const cf4v*)seg_quads;
-    const f4v org = hq[0];
-    ax = ax - org.x; ay = ay - org.y; az = az - org.z;
-    bx = bx - org.x; by = by - org.y; bz = bz - org.z;
-    const bool fa = __builtin_isfinite(ax) && __builtin_isfinite(ay) && __builtin_isfinite(az);
-    const bool fb = __builtin_isfinite(bx) && __builtin_isfinite(by) && __builtin_isfinite(bz);
-    const cf4v* tq = hq + 4;
-    const f2v ax2 = {ax, ax}, ay2 = {ay, ay}, az2 = {az, az};
-    const f2v bx2 = {bx, bx}, by2 = {by, by}, bz2 = {bz, bz};
-    float aA = INFINITY, aB = INFINITY, bA = INFINITY, bB = INFINITY;
-    int oaA = -1, oaB = -1, obA = -1, obB = -1;
-    auto qmin2 = [&](const cf4v* q, float& ma, float& mb) {
-        const f4v X = q[0], Y = q[1], Z = q[2], T = q[3];
-        const f2v ka = __builtin_elementwise_fma(X.xy, ax2, __builtin_elementwise_fma(Y.xy, ay2,
-                                                  __builtin_elementwise_fma(Z.xy, az2, T.xy)));
-        const f2v kb = __builtin_elementwise_fma(X.zw, ax2, __builtin_elementwise_fma(Y.zw, ay2,
-                                                  __builtin_elementwise_fma(Z.zw, az2, T.zw)));
-        ma = fminf(fminf(fminf(ka.x, ka.y), kb.x), kb.y);
-        const f2v la = __builtin_elementwise_fma(X.xy, bx2, __builtin_elementwise_fma(Y.xy, by2,
-                                                  __builtin_elementwise_fma(Z.xy, bz2, T.xy)));
-        const f2v lb = __builtin_elementwise_fma(X.zw, bx2, __builtin_elementwise_fma(Y.zw, by2,
-                                                  __builtin_elementwise_fma(Z.zw, bz2, T.zw)));
-        mb = fminf(fminf(fminf(la.x, la.y), lb.x), lb.y);
-    };
-    int o = 0;
-    const cf4v* q = tq;
-#pragma unroll PCORE_SCAN2_UNROLL
-    for (; o + 2 <= nq; o += 2, q += 8) {
-        float ma, mb;
-        qmin2(q, ma, mb);
-        if (ma < aA) { aA = ma; oaA = o; }
-        if (mb < bA) { bA = mb; obA = o; }
-        qmin2(q + 4, ma, mb);
-        if (ma < aB) { aB = ma; oaB = o + 1; }
-        if (mb < bB) { bB = mb; obB = o + 1; }
-    }
-    if (o < nq) {
-        float ma, mb;
-        qmin2(q, ma, mb);
-        if (ma < aA) { aA = ma; oaA = o; }
-        if (mb < bA) { bA = mb; obA = o; }
-    }
-    if (aB < aA || (aB == aA && oaB >= 0 && oaB < oaA)) { aA = aB; oaA = oaB; }
-    if (bB < bA || (bB == bA && obB >= 0 && obB < obA)) { bA = bB; obA = obB; }
-    auto element1 = [&](int oq, float m, float qx, float qy, float qz, int& k) {  // first key == m in quad oq, or 4
-        const float* Q = seg_quads + 16 + 16 * oq;
-        const float4 X = *reinterpret_cast<const float4*>(Q), Y = *reinterpret_cast<const float4*>(Q + 4);
-        const float4 Z = *reinterpret_cast<const float4*>(Q + 8), T = *reinterpret_cast<const float4*>(Q + 12);
-        k = gicpm::nn_key(X.x, Y.x, Z.x, T.x, qx, qy, qz) == m ? 0
-          : gicpm::nn_key(X.y, Y.y, Z.y, T.y, qx, qy, qz) == m ? 1
-          : gicpm::nn_key(X.z, Y.z, Z.z, T.z, qx, qy, qz) == m ? 2
-          : gicpm::nn_key(X.w, Y.w, Z.w, T.w, qx, qy, qz) == m ? 3 : 4;
-    };
-    auto element = [&](int oq, float m, float qx, float qy, float qz) {
-        int k;
-        element1(oq, m, qx, qy, qz, k);
-        // one of the keys equals m (same FMAs); the clamp only keeps a broken match inside the segment
-        return min(4 * oq + min(k, 3), nt - 1);
-    };
-    ja = fa && aA < INFINITY ? element(oaA, aA, ax, ay, az) : -1;
-    jb = fb && bA < INFINITY ? element(obA, bA, bx, by, bz) : -1;
-}
-
 __device__ __forceinline__ void load_cov(const double* cov, int i, double (&c)[6]) {
     const double2* c2 = reinterpret_cast<const double2*>(cov + (size_t)6 * i);
     const double2 a = c2[0], b = c2[1], d = c2[2];
     c[0] = a.x; c[1] = a.y; c[2] = b.x; c[3] = b.y; c[4] = d.x; c[5] = d.y;
-}
-
-// a wave-uniform double moved to SGPRs (R, t of the pose being refined, the LM scalars)
-__device__ __forceinline__ double uniform_d(double x) {
-    const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ float uniform_f(float x) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(unsigned, x)));
-}
-
-// The wave shuffle-down tree of the 28 normal-equation sums (the oracle's order: node(l, off) = node(l, 2 off) +
-// node(l + off, 2 off) for off = 32 ... 1, node(l, 64) = lane l's entry, so lane 0's sums ((x0 + x32) + (x16 + x48))
-// + ... ), computed in registers with the values split between the halves at every level: at offset o the lanes of
-// each 2o-block pair two registers A, B; the lower half adds its partner's A and keeps value A, the upper half adds
-// its partner's B and keeps value B.  Lane l then holds node(l mod o, o) of half as many values, so the wave does
-// 16 + 8 + 4 + 2 + 1 + 1 adds instead of 28 x 6.  The sums are the tree's own (IEEE addition commutes), whichever lane
-// forms them: value v ends on lane 2 v.  Offsets 32 and 16 swap halves with v_permlane32_swap / v_permlane16_swap,
-// 8 and 4 use DPP row shifts written bank by bank, 2 and 1 quad permutations.  (Round 3 transposed the partial sums
-// through 7.4 KB of LDS per wave and summed them on 14 lanes: 5.6 k of ~36 k clocks per pose-iteration.)
-template <int CTRL, int ROWS, int BANKS>
-__device__ __forceinline__ double dpp_d(double old, double src) {
-    const unsigned long long o = __builtin_bit_cast(unsigned long long, old);
-    const unsigned long long v = __builtin_bit_cast(unsigned long long, src);
-    const unsigned lo = __builtin_amdgcn_update_dpp((unsigned)o, (unsigned)v, CTRL, ROWS, BANKS, false);
-    const unsigned hi = __builtin_amdgcn_update_dpp((unsigned)(o >> 32), (unsigned)(v >> 32), CTRL, ROWS, BANKS, false);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-template <bool ROWS16>
-__device__ __forceinline__ double swap_add(double a, double b) {  // offsets 32 (ROWS16 false) and 16
-    const unsigned long long ua = __builtin_bit_cast(unsigned long long, a);
-    const unsigned long long ub = __builtin_bit_cast(unsigned long long, b);
-    unsigned alo = (unsigned)ua, ahi = (unsigned)(ua >> 32), blo = (unsigned)ub, bhi = (unsigned)(ub >> 32);
-    if constexpr (ROWS16) {
-        const auto l = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-        alo = l[0]; blo = l[1]; ahi = h[0]; bhi = h[1];
-    } else {
-        const auto l = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
-        const auto h = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
-        alo = l[0]; blo = l[1]; ahi = h[0]; bhi = h[1];
-    }
-    return __builtin_bit_cast(double, ((unsigned long long)ahi << 32) | alo) +
-           __builtin_bit_cast(double, ((unsigned long long)bhi << 32) | blo);
-}
-template <int OFF>
-__device__ __forceinline__ double bank_add(double a, double b) {  // offsets 8 (banks 0-1 | 2-3) and 4 (0, 2 | 1, 3)
-    constexpr int LOW = OFF == 8 ? 0x3 : 0x5;
-    const double t = dpp_d<0x110 + OFF, 0xf, 0xf ^ LOW>(dpp_d<0x100 + OFF, 0xf, LOW>(0.0, a), b);  // row_shl / row_shr
-    const double u = dpp_d<0xE4, 0xf, 0xf ^ LOW>(a, b);                                            // own value
-    return u + t;
-}
-__device__ __forceinline__ const double* wave_tree_sums(const double (&acc)[gicpm::kTerms], double* out, int lane) {
-    constexpr int K = gicpm::kTerms;
-    static_assert(K > 16 && K <= 32, "28 sums: 16 register pairs at offset 32");
-    double r[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) r[k] = swap_add<false>(acc[k], k + 16 < K ? acc[k + 16] : 0.0);
-#pragma unroll
-    for (int k = 0; k < 8; k++) r[k] = swap_add<true>(r[k], r[k + 8]);
-#pragma unroll
-    for (int k = 0; k < 4; k++) r[k] = bank_add<8>(r[k], r[k + 4]);
-#pragma unroll
-    for (int k = 0; k < 2; k++) r[k] = bank_add<4>(r[k], r[k + 2]);
-    {  // offset 2: lanes 0-1 of a quad keep r0, lanes 2-3 r1
-        const bool up = lane & 2;
-        const double sel = up ? r[0] : r[1], own = up ? r[1] : r[0];
-        r[0] = own + dpp_d<0x4E, 0xf, 0xf>(0.0, sel);  // quad_perm [2, 3, 0, 1]
-    }
-    r[0] = r[0] + dpp_d<0xB1, 0xf, 0xf>(0.0, r[0]);    // offset 1: quad_perm [1, 0, 3, 2]
-    // (the slot's address formed here, not hoisted out of the iteration loop into a register that gets spilled)
-    if (!(lane & 1) && (lane >> 1) < K) out[(lane >> 1) + opaque_zero()] = r[0];
-    wave_lds_sync();
-    return out;
-}
-
-// Lane 0's value of the wave shuffle-down tree x <- x + shfl_down(x, off), off = 32 ... 1 (the oracle's reduction
-// order: ((x0 + x32) + (x16 + x48)) + ...), without the LDS pipe: the 32- and 16-lane levels through
-// v_permlane32_swap / v_permlane16_swap (lane l < 32 receives lane l + 32, lane l of an even row lane l + 16), the
-// 8 ... 1 levels through DPP row_shl (lane l of a row receives lane l + off).  Other lanes end with partial sums
-// (read lane 0).
-__device__ __forceinline__ double wave_sum_lane0(double x) {
-    auto halves = [](double v, unsigned& lo, unsigned& hi) {
-        const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-        lo = (unsigned)u;
-        hi = (unsigned)(u >> 32);
-    };
-    auto join = [](unsigned lo, unsigned hi) {
-        return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-    };
-    unsigned lo, hi;
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_permlane32_swap(lo, lo, false, false)[1],
-                 __builtin_amdgcn_permlane32_swap(hi, hi, false, false)[1]);
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_permlane16_swap(lo, lo, false, false)[1],
-                 __builtin_amdgcn_permlane16_swap(hi, hi, false, false)[1]);
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_update_dpp(0u, lo, 0x108, 0xf, 0xf, false),   // row_shl:8
-                 __builtin_amdgcn_update_dpp(0u, hi, 0x108, 0xf, 0xf, false));
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_update_dpp(0u, lo, 0x104, 0xf, 0xf, false),   // row_shl:4
-                 __builtin_amdgcn_update_dpp(0u, hi, 0x104, 0xf, 0xf, false));
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_update_dpp(0u, lo, 0x102, 0xf, 0xf, false),   // row_shl:2
-                 __builtin_amdgcn_update_dpp(0u, hi, 0x102, 0xf, 0xf, false));
-    halves(x, lo, hi);
-    x = x + join(__builtin_amdgcn_update_dpp(0u, lo, 0x101, 0xf, 0xf, false),   // row_shl:1
-                 __builtin_amdgcn_update_dpp(0u, hi, 0x101, 0xf, 0xf, false));
-    return x;
 }
 
 // the pose's state in double: rotation and translation of the GICP transform (source -> target, metres)
@@ -676,39 +247,18 @@ struct Round0 {
     float4* t;
 };
 
-// Linearisation of one round of 64 source points (point i on lane i % 64), fast_gicp linearize /
-// update_correspondences: the correspondence of the float query, then -- for points with one -- the shared
-// contribution into acc; the correspondence and M go to the iteration's scratch (corr[i], mah[6 i ..]) for the
-// trials' errors.
-template <bool STORE_CORR>
-__device__ __forceinline__ void linearize_round(const Xform& x, const float (&Rf)[3][3], const float (&tf)[3],
-                                                const float4* src, const double* scov, const float4* tgt,
-                                                const double* tcov, int ns, int i, bool use_grid, const LabelGrid& G,
-                                                const GicpArgs& g, const float* tquads, int nt, int j_in,
-                                                int32_t* corr, double* mah, const Round0& r0,
-                                                double (&acc)[gicpm::kTerms], bool search GPROF_PARAM) {
+// Linearisation of one round of 64 source points (point i on lane i % 64; j: its correspondence, found by the caller,
+// or -1), fast_gicp linearize: for points with a correspondence the shared contribution into acc, and M to the wave's
+// LDS (r0) or the iteration's scratch (mah[6 i ..]) for the trials' errors.
+__device__ __forceinline__ void linearize_round(const Xform& x, const float4* src, const double* scov,
+                                                const float4* tgt, const double* tcov, int ns, int i, int j,
+                                                double* mah, const Round0& r0,
+                                                double (&acc)[gicpm::kTerms] GPROF_PARAM) {
     GPROF_T(t_s0);
     const bool act = i < ns;
     const float4 sp = act ? src[i] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    int j = j_in;
-    if (STORE_CORR && !search) {
-        j = act ? corr[i] : -1;  // the iteration's set from the correspondence history (gicp_kernel)
-    } else if (STORE_CORR) {
-        float qf[3];
-        gicpm::query_f(Rf, tf, sp.x, sp.y, sp.z, qf);
-        // correspondence: first strict minimum of the key (segments <= kKeyScanMax) or of the float squared
-        // distance (grid search of larger segments), as orc_gicp
-        float best = INFINITY;
-        j = -1;
-        if (use_grid) {
-            if (act) grid_nn(G, g.cell_start, g.grid_pts, tgt, nt, qf[0], qf[1], qf[2], best, j);
-        } else {
-            scan_quads(tquads, nt, qf[0], qf[1], qf[2], best, j);
-        }
-        if (act) corr[i] = j;
-    }
     GPROF_TD(t_s1, j);
-    GPROF_ADD(0, t_s0, t_s1);
+    GPROF_ADD(0, t_s0, t_s1);  // the search is the caller's: its wait for j, if any, counts as search
     const bool first = i < kLdsPts;  // a point of the rounds kept in LDS
     if (first && !(act && j >= 0)) r0.t[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (act && j >= 0) {
@@ -737,14 +287,12 @@ __device__ __forceinline__ void linearize_round(const Xform& x, const float (&Rf
     GPROF_ADD(1, t_s1, t_s2);
 }
 
-
 // One Levenberg-Marquardt iteration of one wave (LsqRegistration::step_lm) on the reduced system `sys` (28 sums in
 // LDS: upper H, b, the error y0 at x): up to kLmMaxTrials solves of (H + lambda I) d = -b, each scored by the error
 // at delta * x with the iteration's correspondences and M (point i on lane i % 64, summed by the shuffle-down tree).
 // Every lane runs the same uniform arithmetic; the scalars that steer it are moved to SGPRs.
-template <typename CorrPtr>
 __device__ __forceinline__ int lm_iteration(const double* sys, Xform& x, double& lambda, const float4* src,
-                                            CorrPtr corr, const double* mah, const float4* tgt, int ns, int lane,
+                                            const int32_t* corr, const double* mah, const float4* tgt, int ns, int lane,
                                             const Round0& r0, const lds_cvd* se3c, double rot_eps,
                                             double trans_eps, bool& inert GPROF_PARAM) {
     const double y0 = uniform_d(sys[gicpm::kErr]);
@@ -842,106 +390,6 @@ __device__ __forceinline__ void write_pose(const GicpArgs& g, int gp, const Xfor
     if (g.iters_out) g.iters_out[gp] = iters;
 }
 
-__device__ __forceinline__ void xform_float(const Xform& x, float (&Rf)[3][3], float (&tf)[3]) {
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-#pragma unroll
-        for (int c = 0; c < 3; c++) Rf[r][c] = uniform_f((float)x.R[r][c]);
-        tf[r] = uniform_f((float)x.t[r]);
-    }
-}
-
-// A 16-slot ring of float transforms in LDS (the correspondence history and the cycle exit): lane l holds components
-// 3 (l & 3) + v (v = 0, 1, 2) of slot l >> 2 in word v (R rows 0..2, then t), as bit patterns (-0 != +0, NaN == NaN).
-__device__ __forceinline__ void xf_lane_words(const float (&Rf)[3][3], const float (&tf)[3], int sub, unsigned& b0,
-                                              unsigned& b1, unsigned& b2) {
-    const float c0 = sub == 0 ? Rf[0][0] : sub == 1 ? Rf[1][0] : sub == 2 ? Rf[2][0] : tf[0];
-    const float c1 = sub == 0 ? Rf[0][1] : sub == 1 ? Rf[1][1] : sub == 2 ? Rf[2][1] : tf[1];
-    const float c2 = sub == 0 ? Rf[0][2] : sub == 1 ? Rf[1][2] : sub == 2 ? Rf[2][2] : tf[2];
-    b0 = __builtin_bit_cast(unsigned, c0);
-    b1 = __builtin_bit_cast(unsigned, c1);
-    b2 = __builtin_bit_cast(unsigned, c2);
-}
-
-// bit s set: all four lanes of slot s hold (b0, b1, b2) (the lanes' current words hv0..hv2)
-__device__ __forceinline__ unsigned ring_match16(unsigned b0, unsigned b1, unsigned b2, unsigned hv0, unsigned hv1,
-                                                 unsigned hv2) {
-    unsigned long long eq = __ballot(b0 == hv0 && b1 == hv1 && b2 == hv2);
-    eq = eq & (eq >> 1) & (eq >> 2) & (eq >> 3) & 0x1111111111111111ull;  // bit 4s: slot s
-    eq = (eq | (eq >> 3)) & 0x0303030303030303ull;                         // gather bit 4s to bit s
-    eq = (eq | (eq >> 6)) & 0x000f000f000f000full;
-    eq = (eq | (eq >> 12)) & 0x000000ff000000ffull;
-    eq = (eq | (eq >> 24)) & 0xffffull;
-    return (unsigned)eq;
-}
-
-// The cycle exit (pcore_gicp_math.h cycle_update) of one wave: the last 32 float transforms T_f(j) in slot
-// (j - 1) % 32 of an LDS ring of two 16-slot banks (words 0..2: slots 0..15, words 3..5: slots 16..31, each bank laid out
-// as xf_lane_words), the slots written so far and the run counters.
-static_assert(gicpm::kCycleLags == 32, "CycleExit holds 32 slots");
-constexpr int kCycleRingWords = 6 * 64;
-
-struct CycleExit {
-    unsigned* ring;  // kCycleRingWords, this wave's
-    unsigned written;
-    gicpm::CycleRun run;
-
-    __device__ __forceinline__ void start(int lane) {  // T_f(1) = float(identity) in slot 0
-        // lane l < 4 writes row l of I (t = 0 for l = 3): word v is 1.0f where v == l; formed here from an opaque lane
-        // index, or the compiler hoists the words and addresses out of the persistent pose loop and holds 4 VGPRs
-        const int l = lane + opaque_zero();
-        if (l < 4) {  // every lane reads back only the words it wrote itself
-            ring[l] = l == 0 ? 0x3f800000u : 0u;
-            ring[64 + l] = l == 1 ? 0x3f800000u : 0u;
-            ring[128 + l] = l == 2 ? 0x3f800000u : 0u;
-        }
-        written = 1u;
-        run = {0, 0, 0};
-    }
-
-    // after iteration `iters`' accepted step (iters < max_iter): T_f(iters + 1) = float(x).  Returns -1, or the ring slot
-    // of the cycle member the pose stops with (read by `member` once the loop has ended).
-    __device__ __forceinline__ int step(const Xform& x, int iters, int max_iter, int window, bool inert, int lane_) {
-        const int lane = lane_ + opaque_zero();  // per-lane values formed here, not hoisted out of the iteration loop
-        float Rf[3][3], tf[3];
-        xform_float(x, Rf, tf);
-        unsigned b0, b1, b2;
-        xf_lane_words(Rf, tf, lane & 3, b0, b1, b2);
-        const int cur = iters + 1, c0 = (cur - 1) & 31, bank = c0 >> 4;
-        const unsigned m0 = ring_match16(b0, b1, b2, ring[lane], ring[64 + lane], ring[128 + lane]);
-        const unsigned m1 = ring_match16(b0, b1, b2, ring[192 + lane], ring[256 + lane], ring[320 + lane]);
-        const unsigned m = (m0 | (m1 << 16)) & written;
-        // lag q lives in slot (c0 - q) % 32: in the doubled mask at c0 + 32 - q, so the smallest lag is the highest bit
-        const unsigned long long mm = (unsigned long long)m | ((unsigned long long)m << 32);
-        const unsigned t = (unsigned)(mm >> c0);
-        const int p = t ? 32 - (31 - __builtin_clz(t)) : 0;
-        if ((lane >> 2) == (c0 & 15)) {
-            unsigned* w = ring + 192 * bank + lane;
-            w[0] = b0;
-            w[64] = b1;
-            w[128] = b2;
-        }
-        written |= 1u << c0;
-        if (!gicpm::cycle_update(run, p, inert, window)) return -1;
-        return (gicpm::cycle_member(cur, p, max_iter) - 1) & 31;
-    }
-
-    // the float transform of ring slot s as the pose's result (after the loop: x is written back, not iterated on; the
-    // ring was written by the whole wave, read here by every lane)
-    __device__ __forceinline__ void member(int s, Xform& x) {
-        wave_lds_sync();
-        const unsigned* w = ring + 192 * (s >> 4) + 4 * (s & 15);
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-#pragma unroll
-            for (int v = 0; v < 3; v++) {
-                const double f = (double)__builtin_bit_cast(float, w[64 * v + r]);
-                if (r < 3) x.R[r][v] = f;
-                else x.t[v] = f;
-            }
-    }
-};
-
 // the launch's iteration counters (GicpArgs::iter_stats): no-return atomics, one lane per pose
 __device__ __forceinline__ void count_iterations(const GicpArgs& g, int reported, int run, bool exited) {
     if (!g.iter_stats) return;
@@ -950,9 +398,26 @@ __device__ __forceinline__ void count_iterations(const GicpArgs& g, int reported
     if (exited) __hip_atomic_fetch_add(g.iter_stats + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// A pose's end, by one lane: the refined pose with the iterations it reports, the launch's counters and the timeline
+// stamp.  iters_run: the iterations executed when a cycle exit stopped the pose (which then reports max_iter), else 0.
+__device__ __forceinline__ void finish_pose(const GicpArgs& g, int gp, const Xform& x, int iters,
+                                            int iters_run GTL_PARAM(tl_p0)) {
+    const int run = iters_run ? iters_run : iters;
+    write_pose(g, gp, x, iters);
+    count_iterations(g, iters, run, iters_run != 0);
+    GTL_POSE(gp, tl_p0, run);
+}
+
+// The next pose of the launch's queue (chunk-local; num_poses or more: the queue is empty), by one lane: the queue is
+// ordered longest first where the host sorted it (launch_gicp_order).
+__device__ __forceinline__ int pop_pose(const GicpArgs& g, int num_poses) {
+    const int q = atomicAdd(g.work_counter, 1);
+    return (g.pose_order && q < num_poses) ? g.pose_order[q] : q;
+}
+
 // the pose a GICP workgroup works on next and its target segment
 struct GicpPose {
-    int pose, gp, ns, nt, seg;
+    int gp, ns, nt, seg;
     const float4* src;
     const double* scov;
     const double* tcov;
@@ -965,7 +430,6 @@ struct GicpPose {
 
 __device__ __forceinline__ GicpPose gicp_pose(const GicpArgs& g, int pose) {
     GicpPose p;
-    p.pose = pose;
     p.gp = g.pose_base + pose;
     p.ns = g.src_count[pose];
     p.src = g.src + (size_t)pose * g.src_cap;
@@ -995,17 +459,15 @@ constexpr int kCycleExited = 3;  // coop_pose's flag: wave 0's cycle exit stoppe
 // the LM iteration exactly as the one-wave path does -- point i on lane i % 64, in point order -- so the refined pose
 // is bit-identical; x and the iteration's outcome reach the other waves through LDS (sX, sFlag).  `r0`, `sRed`, `ring`:
 // wave 0's LDS.  Every thread of the workgroup calls this; thread 0 writes the pose.
-template <bool GRID, int NW, typename Corr>
-__device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, int wave, int lane, Corr corr,
+template <int NW>
+__device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, int wave, int lane, int32_t* corr,
                                           double* sRed, const Round0& r0, const lds_cvd* se3c, unsigned* ring,
                                           double* sX, int* sFlag GPROF_PARAM) {
     constexpr int NT = 64 * NW;
     const int tid = wave * 64 + lane;
-#ifdef PCORE_GICP_TIMELINE
-    const unsigned long long tl_p0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    GTL_NOW(tl_p0);
     LabelGrid G{};
-    if (GRID && P.use_grid) G = g.grids[P.seg];
+    if (P.use_grid) G = g.grids[P.seg];
     Xform x;
     xform_identity(x);
     double lambda = -1.0;  // wave 0's
@@ -1017,7 +479,7 @@ __device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, 
     for (int it = 0; run && it < g.max_iter; it++) {
         iters++;
         float Rf[3][3], tf[3];
-        xform_float(x, Rf, tf);
+        xform_float(x.R, x.t, Rf, tf);
         GPROF_T(t_w0);
         // correspondences, all waves
         for (int i0 = wave * 64; i0 < P.ns; i0 += NT) {
@@ -1028,7 +490,7 @@ __device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, 
             gicpm::query_f(Rf, tf, sp.x, sp.y, sp.z, qf);
             int j = -1;
             float best = INFINITY;
-            if (GRID && P.use_grid) {
+            if (P.use_grid) {
                 if (act) grid_nn(G, g.cell_start, g.grid_pts, P.tgt, P.nt, qf[0], qf[1], qf[2], best, j);
             } else {
                 scan_quads(P.tquads, P.nt, qf[0], qf[1], qf[2], best, j);
@@ -1044,8 +506,8 @@ __device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, 
             for (int v = 0; v < gicpm::kTerms; v++) acc[v] = 0.0;
             for (int i0 = 0; i0 < P.ns; i0 += 64) {
                 const int i = i0 + lane;
-                linearize_round<false>(x, Rf, tf, P.src, P.scov, P.tgt, P.tcov, P.ns, i, P.use_grid, G, g, P.tquads,
-                                       P.nt, i < P.ns ? corr[i] : -1, nullptr, P.mah, r0, acc, false GPROF_ARG);
+                linearize_round(x, P.src, P.scov, P.tgt, P.tcov, P.ns, i, i < P.ns ? corr[i] : -1, P.mah, r0,
+                                acc GPROF_ARG);
             }
             GPROF_TD(t_w2, acc[0]);
             const double* sys = wave_tree_sums(acc, sRed, lane);
@@ -1057,9 +519,9 @@ __device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, 
             GPROF_ADD(2, t_w2, t_w3);  // [1]: linearize_round's own marks
             GPROF_ADD(3, t_w3, t_w4);
             if (st == gicpm::kLmAccepted && g.cycle_window > 0 && iters < g.max_iter) {
-                const int s2 = cyc.step(x, iters, g.max_iter, g.cycle_window, inert, lane);
+                const int s2 = cyc.step(x.R, x.t, iters, g.max_iter, g.cycle_window, inert, lane);
                 if (s2 >= 0) {
-                    cyc.member(s2, x);
+                    cyc.member(s2, x.R, x.t);
                     st = kCycleExited;
                 }
             }
@@ -1088,17 +550,7 @@ __device__ __forceinline__ void coop_pose(const GicpArgs& g, const GicpPose& P, 
         if (flag != gicpm::kLmAccepted) break;
     }
     __syncthreads();
-    if (tid == 0) {
-        write_pose(g, P.gp, x, iters);
-        count_iterations(g, iters, iters_run ? iters_run : iters, iters_run != 0);
-#ifdef PCORE_GICP_TIMELINE
-        if (P.gp < kTlPoses) {
-            g_tl_pose[2 * P.gp] = tl_p0;
-            g_tl_pose[2 * P.gp + 1] = __builtin_amdgcn_s_memrealtime();
-            g_tl_run[P.gp] = iters_run ? iters_run : iters;
-        }
-#endif
-    }
+    if (tid == 0) finish_pose(g, P.gp, x, iters, iters_run GTL_ARG(tl_p0));
 }
 
 // One wave per pose; persistent waves pull poses from a counter.  Each iteration linearises in rounds of 64
@@ -1127,29 +579,18 @@ gicp_kernel(GicpArgs g, int num_poses) {
     const Round0 r0{sM0, sS0, sT0};
     if (threadIdx.x < 4 * gicpm::kSe3Terms) sSe3[threadIdx.x] = gicpm::kSe3Coef[threadIdx.x];
     GPROF_DECL;
-#ifdef PCORE_GICP_TIMELINE
-    const unsigned long long tl_w0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    GTL_NOW(tl_w0);
     for (;;) {
         wave_lds_sync();  // the previous pose's reads of sPose are done
-        if (lane == 0) {
-            const int q = atomicAdd(g.work_counter, 1);
-            sPose = (g.pose_order && q < num_poses) ? g.pose_order[q] : q;
-        }
+        if (lane == 0) sPose = pop_pose(g, num_poses);
         wave_lds_sync();
         const int pose = __builtin_amdgcn_readfirstlane(sPose);  // chunk-local, uniform
         if (pose >= num_poses) break;
         const GicpPose P = gicp_pose(g, pose);
         if (!GRID && P.use_grid && lane == 0 && g.iter_stats)  // the host picked the instance without the search
             __hip_atomic_fetch_add(g.iter_stats + 3, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef PCORE_GICP_TIMELINE
-        const unsigned long long tl_p0 = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef PCORE_GICP_PROFILE
-        unsigned long long gp_snap[kGprof];  // the sums before this pose (restored if the pose is below the size filter)
-        for (int k_ = 0; k_ < kGprof; k_++) gp_snap[k_] = gp_acc[k_];
-#endif
-        const LabelGrid G{};  // linearize_round's grid argument, unused here: the searches below load the grid
+        GTL_NOW(tl_p0);
+        GPROF_POSE_BEGIN;
         Xform x;
         xform_identity(x);
         double lambda = -1.0;
@@ -1170,7 +611,7 @@ gicp_kernel(GicpArgs g, int num_poses) {
             for (int it = 0; it < g.max_iter; it++) {
                 iters++;
                 float Rf[3][3], tf[3];
-                xform_float(x, Rf, tf);
+                xform_float(x.R, x.t, Rf, tf);
                 int32_t* cset = P.corr;
                 bool reuse = false;
                 if (hist) {
@@ -1197,9 +638,7 @@ gicp_kernel(GicpArgs g, int num_poses) {
                     }
                     cset = hbase + (size_t)__builtin_amdgcn_readfirstlane(e) * g.corr_hist_cap;
                 }
-#ifdef PCORE_GICP_PROFILE
-                gp_acc[8] += reuse ? 1ull : 0ull;
-#endif
+                GPROF_COUNT(8, reuse ? 1ull : 0ull);
                 double acc[gicpm::kTerms];
 #pragma unroll
                 for (int v = 0; v < gicpm::kTerms; v++) acc[v] = 0.0;
@@ -1226,13 +665,8 @@ gicp_kernel(GicpArgs g, int num_poses) {
                             if (ia < P.ns) grid_nn(Gs, g.cell_start, g.grid_pts, P.tgt, P.nt, qa[0], qa[1], qa[2], best, ja);
                             if (two && ib < P.ns)
                                 grid_nn(Gs, g.cell_start, g.grid_pts, P.tgt, P.nt, qb[0], qb[1], qb[2], best, jb);
-                        } else if (two && PCORE_GICP_PAIR_SCAN) {
+                        } else if (two) {
                             scan_quads2(P.tquads, P.nt, qa[0], qa[1], qa[2], qb[0], qb[1], qb[2], ja, jb);
-                        } else if (two) {  // A/B: the pair's queries scanned one after the other
-                            float best = INFINITY;
-                            scan_quads(P.tquads, P.nt, qa[0], qa[1], qa[2], best, ja);
-                            best = INFINITY;
-                            scan_quads(P.tquads, P.nt, qb[0], qb[1], qb[2], best, jb);
                         } else {
                             float best = INFINITY;
                             scan_quads(P.tquads, P.nt, qa[0], qa[1], qa[2], best, ja);
@@ -1242,12 +676,11 @@ gicp_kernel(GicpArgs g, int num_poses) {
                     }
                     GPROF_TD(t_s1, ja + jb);
                     GPROF_ADD(0, t_s0, t_s1);
-                    linearize_round<false>(x, Rf, tf, P.src, P.scov, P.tgt, P.tcov, P.ns, ia, P.use_grid, G, g,
-                                           P.tquads, P.nt, ia < P.ns ? ja : -1, nullptr, P.mah, r0, acc, false GPROF_ARG);
+                    linearize_round(x, P.src, P.scov, P.tgt, P.tcov, P.ns, ia, ia < P.ns ? ja : -1, P.mah, r0,
+                                    acc GPROF_ARG);
                     if (two)
-                        linearize_round<false>(x, Rf, tf, P.src, P.scov, P.tgt, P.tcov, P.ns, ib, P.use_grid, G, g,
-                                               P.tquads, P.nt, ib < P.ns ? jb : -1, nullptr, P.mah, r0, acc,
-                                               false GPROF_ARG);
+                        linearize_round(x, P.src, P.scov, P.tgt, P.tcov, P.ns, ib, ib < P.ns ? jb : -1, P.mah, r0,
+                                        acc GPROF_ARG);
                 }
                 GPROF_T(t_b);
                 const double* sys = wave_tree_sums(acc, sRed, lane);
@@ -1260,7 +693,7 @@ gicp_kernel(GicpArgs g, int num_poses) {
                 GPROF_ADD(3, t_c, t_d);
                 if (st != gicpm::kLmAccepted) break;
                 if (g.cycle_window > 0 && iters < g.max_iter) {
-                    exit_slot = cyc.step(x, iters, g.max_iter, g.cycle_window, inert, lane);
+                    exit_slot = cyc.step(x.R, x.t, iters, g.max_iter, g.cycle_window, inert, lane);
                     if (exit_slot >= 0) {
                         iters_run = iters;
                         iters = g.max_iter;
@@ -1269,36 +702,13 @@ gicp_kernel(GicpArgs g, int num_poses) {
                 }
             }
         }
-        if (exit_slot >= 0) cyc.member(exit_slot, x);
-#ifdef PCORE_GICP_PROFILE
-        gp_acc[9] += iters_run ? iters_run : iters;
-        if (P.ns < PCORE_GICP_PROF_MIN_NS)
-            for (int k_ = 0; k_ < kGprof; k_++) gp_acc[k_] = gp_snap[k_];
-#endif
-        if (lane == 0) {
-            write_pose(g, P.gp, x, iters);
-            count_iterations(g, iters, iters_run ? iters_run : iters, iters_run != 0);
-        }
-#ifdef PCORE_GICP_TIMELINE
-        if (lane == 0 && P.gp < kTlPoses) {
-            g_tl_pose[2 * P.gp] = tl_p0;
-            g_tl_pose[2 * P.gp + 1] = __builtin_amdgcn_s_memrealtime();
-            g_tl_run[P.gp] = iters_run ? iters_run : iters;
-        }
-#endif
+        if (exit_slot >= 0) cyc.member(exit_slot, x.R, x.t);
+        GPROF_POSE_END(P.ns, iters_run ? iters_run : iters);
+        if (lane == 0) finish_pose(g, P.gp, x, iters, iters_run GTL_ARG(tl_p0));
     }
     GPROF_FLUSH;
-#ifdef PCORE_GICP_TIMELINE
-    if (lane == 0) {
-        const unsigned int w = atomicAdd(&g_tl_nwaves, 1u);
-        if (w < (unsigned)kTlWaves) {
-            g_tl_wave[2 * w] = tl_w0;
-            g_tl_wave[2 * w + 1] = __builtin_amdgcn_s_memrealtime();
-        }
-    }
-#endif
+    GTL_WAVE(tl_w0);
 }
-
 
 // Small batches (C1: 128 poses fill 128 of 1024 SIMDs) with large target segments: WPP waves per pose.
 // All waves search the correspondences of the iteration's source points (round r -> wave r % WPP), the
@@ -1322,32 +732,18 @@ __global__ void __launch_bounds__(64 * WPP) gicp_wide_kernel(GicpArgs g, int num
     GPROF_DECL;  // wave 0's phases: [0] the searches of all waves (to the barrier), [1] contributions, [2] tree, [3] LM
     for (;;) {
         __syncthreads();
-        if (tid == 0) {
-            const int q = atomicAdd(g.work_counter, 1);
-            sPose = (g.pose_order && q < num_poses) ? g.pose_order[q] : q;
-        }
+        if (tid == 0) sPose = pop_pose(g, num_poses);
         __syncthreads();
         const int pose = __builtin_amdgcn_readfirstlane(sPose);
         if (pose >= num_poses) break;
-        coop_pose<true, WPP>(g, gicp_pose(g, pose), wave, lane, jbuf, sRed, r0, (const lds_cvd*)sSe3, sCyc, sX,
-                             &sFlag GPROF_ARG);
+        coop_pose<WPP>(g, gicp_pose(g, pose), wave, lane, jbuf, sRed, r0, (const lds_cvd*)sSe3, sCyc, sX,
+                       &sFlag GPROF_ARG);
     }
     if (wave == 0) GPROF_FLUSH;
 }
 
 constexpr int kGicpWideWpp = 8;
 constexpr size_t kGicpWideMaxLds = 96 * 1024;  // correspondence buffer: src_cap <= 24576
-
-#ifdef PCORE_GICP_PROFILE
-extern "C" int pcore_debug_gicp_profile(unsigned long long* out, int reset) {
-    hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gicp_prof), sizeof(unsigned long long) * kGprof);
-    if (e == hipSuccess && reset) {
-        const unsigned long long z[kGprof] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_gicp_prof), z, sizeof(z));
-    }
-    return e == hipSuccess ? 0 : 1;
-}
-#endif
 
 // Test hook of the kernels' damped solve (gicpm::lm_solve_schur): one wave per 28-term system.
 __global__ void __launch_bounds__(64) lm_solve_test_kernel(const double* sys, const double* lambda, double* out, int n) {

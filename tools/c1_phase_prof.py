@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Per-phase shader clocks of gicp_wide_kernel on C1 (build with -DPCORE_GICP_PROFILE, load with PCORE_LIB): wave 0's
 clocks per pose-iteration in the all-wave correspondence search (to the barrier), the contributions, the 28-term tree
-and the LM iteration (solves, se3_exp + compose, trial errors, decisions)."""
+and the LM iteration (solves, se3_exp + compose, trial errors, decisions).  The phases and their reader are
+csrc/pcore_gicp_probe.h's."""
 import ctypes
 import os
 import sys

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-phase shader clocks of gicp_kernel (build with -DPCORE_GICP_PROFILE, load with PCORE_LIB):
 linearisation (correspondence search + contributions) / 28-term wave reduction / LM iteration (damped solves,
-se3_exp, the trials' error sums), per pose-iteration."""
+se3_exp, the trials' error sums), per pose-iteration.  The phases and their reader are csrc/pcore_gicp_probe.h's."""
 import ctypes
 import os
 import sys

@@ -2,7 +2,8 @@
 """Timeline of one C3 GICP launch (a -DPCORE_GICP_TIMELINE build loaded with PCORE_LIB): per pose, when a wave dequeued
 it and when it finished; per wave, its start and exit (100 MHz real-time clock).  Reports the launch span, the mean
 number of busy waves against the resident maximum, when the queue ran dry (the last dequeue), the tail after it, and
-the iteration counts of the poses that finish in that tail.
+the iteration counts of the poses that finish in that tail.  The stamps and their readers are csrc/pcore_gicp_probe.h's
+(K_POSES, K_WAVES below: its kTlPoses, kTlWaves).
     PCORE_LIB=$PWD/build_ab/tl.so python tools/gicp_timeline.py [--out FILE.json]"""
 import argparse
 import ctypes

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Per-function comparison of the device code of two source trees (no GPU needed):
-    tools/isa_diff.py OLD_TREE [NEW_TREE]      e.g. a `git worktree` of the parent commit and this tree (the default)
+    tools/isa_diff.py [--flags "-D..."] OLD_TREE [NEW_TREE]
+e.g. a `git worktree` of the parent commit and this tree (the default); --flags is appended to both trees' compile
+lines, so measurement builds (-DPCORE_GICP_PROFILE, ...) can be compared too.
 Every entry of each tree's build.SOURCES is compiled device-only with that tree's build.flags(); every function symbol
 (kernels and the device functions the compiler did not inline) is printed with `same` or `differs (N lines)` and the
 new tree's resource usage.  Compared are the instruction streams: `;` comments removed, basic-block label numbers
@@ -22,9 +24,10 @@ def tree_info(tree):
     return out[0], out[1], out[2].split(), [f for f in out[3].split() if f not in ("-shared", "-fPIC")]
 
 
-def functions(tree):
+def functions(tree, extra=()):
     """{symbol: (instruction lines, {resource: value})} over every source of the tree"""
     hipcc, csrc, sources, flags = tree_info(tree)
+    flags = flags + list(extra)
     def compile_one(src):
         with tempfile.NamedTemporaryFile(suffix=".s") as tmp:
             r = subprocess.run([hipcc] + flags + ["--offload-device-only", "-S", os.path.join(csrc, src), "-o", tmp.name,
@@ -69,7 +72,12 @@ def demangle(names):
 
 def main():
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    old, new = functions(sys.argv[1]), functions(sys.argv[2] if len(sys.argv) > 2 else here)
+    args, extra = sys.argv[1:], []
+    if "--flags" in args:
+        i = args.index("--flags")
+        extra = args[i + 1].split()
+        del args[i:i + 2]
+    old, new = functions(args[0], extra), functions(args[1] if len(args) > 1 else here, extra)
     names = sorted(n for n in set(old) | set(new) if "rocprim" not in n)  # the radix sort's kernels are the library's
     pretty, bad = demangle(names), 0
     print(f"{'function':72s} {'result':20s} " + " / ".join(RES))
