@@ -319,6 +319,26 @@ int pcore_render(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_mod
                  int32_t num_poses, float occlusion_threshold, int32_t* d_out_depth, uint8_t* d_out_color,
                  pcore_stream stream);
 
+/* The composed state: every pose into ONE frame, the picture PrintStateGPU draws of the greedy state
+ * (search_env.cpp:1718-1781: render_cuda_multi_unified("RENDER", ..., single_result_image = 1), image_renderer.cuh:
+ * 262-275).  The reference's single image is racy and reads an empty source; the contract here is deterministic
+ * ("Composed state").  With D_i, C_i what pcore_render returns for pose i alone (for occlude = 0:
+ * against an all-zero source, no black-out at all):
+ *   d_out_depth   H x W int32: the minimum D_i[p] over the poses with D_i[p] != 0, else 0
+ *   d_out_owner   H x W int32 (nullable): the lowest i attaining it, else -1 -- a predicted instance mask
+ *   d_out_color   3 x H x W uint8 (nullable), red / green / blue planes: C_owner[p], black without an owner
+ *   d_out_visible num_poses int32 (nullable): the pixels each pose owns
+ * A pose whose nearest fragment at a pixel has depth 0 (a NaN depth of a degenerate triangle, a surface within a
+ * centimetre of the camera's plane) has D_i[p] = 0 and so is absent there: the poses behind it show.
+ * occlude = 1 needs meshes, camera and observation (d_pose_label as in pcore_render); occlude = 0 needs meshes and a
+ * camera only, and d_pose_label must be NULL.  num_poses * num_tris must not exceed 2^32 - 1 (the key of a pixel holds
+ * pose * num_tris + triangle in 32 bits).  num_poses == 0 writes the empty frame.  Model ids outside the meshes render
+ * nothing.  Asynchronous on `stream`, no host readback; every argument is checked before the first launch, and a
+ * refused call writes nothing.  Per-context scratch of 8 B per pixel grows on first use. */
+int pcore_render_scene(pcore_ctx* ctx, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
+                       int32_t num_poses, int32_t occlude, float occlusion_threshold, int32_t* d_out_depth,
+                       uint8_t* d_out_color, int32_t* d_out_owner, int32_t* d_out_visible, pcore_stream stream);
+
 /* gpu_stats of render_cuda_multi_unified (model.h:24-27, filled at renderer.cu:1707 and 1739) for the last
  * pcore_evaluate_icp: icp_runtime = seconds of its GICP stage (source covariances + GICP launches, HIP events on
  * the call's stream -- this call waits for them); peak_memory_usage = the most device memory in use (MB,

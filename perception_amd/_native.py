@@ -30,7 +30,7 @@ COST_DEPTH_6DOF = 2
 EXPORTED_SYMBOLS = (
     "pcore_create", "pcore_destroy", "pcore_last_error", "pcore_abi_version", "pcore_upload_meshes",
     "pcore_set_camera", "pcore_observed_cloud", "pcore_set_observation", "pcore_evaluate", "pcore_evaluate_icp",
-    "pcore_render",
+    "pcore_render", "pcore_render_scene",
     "pcore_depth_to_cloud", "pcore_select", "pcore_pose_distances",
     "pcore_observed_cloud_bounded", "pcore_set_observation_colors", "pcore_generation", "pcore_get_stats",
     "pcore_count_within", "pcore_state_poses", "pcore_evaluate_select", "pcore_get_tile_info", "pcore_debug_lm_solve",
@@ -173,6 +173,8 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
     L.pcore_evaluate_icp.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.POINTER(EvalParams), ctypes.POINTER(IcpParams),
                                      vp, vp, vp, vp, vp, vp]
     L.pcore_render.argtypes = [vp, vp, vp, vp, i32, f32, vp, vp, vp]
+    if hasattr(L, "pcore_render_scene"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_render_scene.argtypes = [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp, vp]
     L.pcore_get_stats.argtypes = [vp, ctypes.POINTER(GpuStats), i32]
     if hasattr(L, "pcore_get_tile_info"):  # diagnostics / test hooks: absent from older A/B builds (PCORE_LIB)
         L.pcore_get_tile_info.argtypes = [vp, ctypes.POINTER(TileInfo)]

@@ -449,6 +449,28 @@ class PoseCore:
             _stream(stream)))
         return (out, out_color) if color else out
 
+    def render_scene(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor] = None,
+                     occlusion_threshold: float = 1.0, occlude: bool = True, color: bool = True, owner: bool = True,
+                     visible: bool = True, stream=None):
+        """The composed state (pcore_render_scene): every pose into one frame.  Returns (depth (H, W) int32 cm, color
+        (3, H, W) uint8 red / green / blue or None, owner (H, W) int32 -- the pose that owns each pixel, -1 for none --
+        or None, visible (N,) int32 -- the pixels each pose owns -- or None).  occlude=False needs no observation and
+        takes no pose_label."""
+        n = int(poses.shape[0])
+        dev = poses.device
+        h, w = self.height, self.width
+        depth = torch.empty((h, w), dtype=torch.int32, device=dev)
+        out_color = torch.empty((3, h, w), dtype=torch.uint8, device=dev) if color else None
+        out_owner = torch.empty((h, w), dtype=torch.int32, device=dev) if owner else None
+        out_visible = torch.empty(n, dtype=torch.int32, device=dev) if visible else None
+        self._check(self.lib.pcore_render_scene(
+            self._h, _ptr(poses, torch.float32, "poses") if n else None,
+            _ptr(pose_model, torch.int32, "pose_model") if n else None, _ptr(pose_label, torch.int32, "pose_label"), n,
+            int(bool(occlude)), float(occlusion_threshold), _ptr(depth, torch.int32, "depth"),
+            _ptr(out_color, torch.uint8, "color"), _ptr(out_owner, torch.int32, "owner"),
+            _ptr(out_visible, torch.int32, "visible") if n else None, _stream(stream)))
+        return depth, out_color, out_owner, out_visible
+
     def stats(self, reset: bool = False) -> dict:
         """pcore_get_stats: the reference's gpu_stats of the last evaluate_icp (waits for its GICP stage)."""
         st = _native.GpuStats()

@@ -281,6 +281,54 @@ int pcore_render(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model
     return PCORE_OK;
 }
 
+int pcore_render_scene(pcore_ctx* c, const float* d_poses, const int32_t* d_pose_model, const int32_t* d_pose_label,
+                       int32_t num_poses, int32_t occlude, float occlusion_threshold, int32_t* d_out_depth,
+                       uint8_t* d_out_color, int32_t* d_out_owner, int32_t* d_out_visible, pcore_stream stream) {
+    if (!c) return PCORE_E_INVALID_ARG;
+    if (!c->have_mesh || !c->have_cam)
+        return fail(c, PCORE_E_STATE, "render_scene: meshes and camera must be set first");
+    if (occlude && !c->have_obs)
+        return fail(c, PCORE_E_STATE, "render_scene: occlude needs an observation");
+    if (num_poses < 0 || !d_out_depth || (num_poses > 0 && (!d_poses || !d_pose_model)))
+        return fail(c, PCORE_E_INVALID_ARG, "render_scene: null pointer");
+    if (d_pose_label && !occlude)
+        return fail(c, PCORE_E_INVALID_ARG, "render_scene: pose labels are read only with occlude");
+    if (d_pose_label && !c->obs_has_mask)
+        return fail(c, PCORE_E_INVALID_ARG, "render_scene: pose labels need a source mask");
+    // the key's low word is pose * num_tris + t, and all-ones stays the empty pixel's
+    if ((uint64_t)num_poses * (uint64_t)c->num_tris > 0xffffffffull)
+        return fail(c, PCORE_E_INVALID_ARG, "render_scene: num_poses * num_tris does not fit the key's 32 bits");
+    HIPC(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int W = c->cam.width, H = c->cam.height;
+    const size_t npx = (size_t)W * H;
+    HIPC(c, dev_reserve(c->scene_keys, npx));
+    HIPC(c, hipMemsetAsync(c->scene_keys.p, 0xff, npx * sizeof(unsigned long long), s));
+    if (d_out_visible && num_poses > 0) HIPC(c, hipMemsetAsync(d_out_visible, 0, (size_t)num_poses * 4, s));
+    SceneArgs a{};
+    a.tris = c->tris.p;
+    a.tri_lo = c->tri_lo.p;
+    a.tri_hi = c->tri_hi.p;
+    a.num_tris = c->num_tris;
+    a.num_models = c->num_models;
+    a.poses = d_poses;
+    a.pose_model = d_pose_model;
+    a.pose_label = d_pose_label;
+    a.num_poses = num_poses;
+    a.width = W;
+    a.height = H;
+    a.proj = c->proj.p;
+    a.src_depth = occlude ? c->src_depth.p : nullptr;
+    a.src_mask = occlude ? c->src_mask.p : nullptr;
+    a.occlude = occlude ? 1 : 0;
+    a.occlusion_threshold = occlusion_threshold;
+    a.keys = c->scene_keys.p;
+    HIPC(c, launch_render_scene(a, s));
+    HIPC(c, launch_scene_finalize(c->scene_keys.p, c->num_tris, num_poses, W, H, c->tri_rgb.p, d_out_depth, d_out_owner,
+                                  d_out_color, d_out_visible, s));
+    return PCORE_OK;
+}
+
 int pcore_debug_lm_solve(const double* d_sys, const double* d_lambda, double* d_out, int32_t n, pcore_stream stream) {
     if (n < 0 || (n > 0 && (!d_sys || !d_lambda || !d_out))) return PCORE_E_INVALID_ARG;
     return launch_lm_solve_test(d_sys, d_lambda, d_out, n, (hipStream_t)stream) == hipSuccess ? PCORE_OK : PCORE_E_HIP;

@@ -124,6 +124,7 @@ struct pcore_ctx {
     // scratch (parity stages)
     DevBuf<int32_t> scratch_counts, scratch_offsets, scratch_total;
     DevBuf<int32_t> render_tri;  // stage RENDER colour: nearest triangle per pixel
+    DevBuf<unsigned long long> scene_keys;  // pcore_render_scene: one (depth, pose, triangle) key per pixel
     // gpu_stats of the last pcore_evaluate_icp (pcore_get_stats): per chunk, events at the source covariances,
     // the GICP launch and its end on the call's stream; the peak device memory in use at a GICP stage
     pcore::Events icp_ev;

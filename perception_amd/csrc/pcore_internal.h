@@ -295,6 +295,29 @@ hipError_t launch_render_finalize(int32_t* depth, const int32_t* src_depth, cons
                                   float occlusion_threshold, hipStream_t s, const int32_t* tri_min = nullptr,
                                   const uint32_t* rgb = nullptr, uint8_t* color = nullptr);
 hipError_t launch_fill_i32(int32_t* p, int32_t v, size_t n, hipStream_t s);
+// composed state (pcore_render_scene): what its raster kernels read, and the keys they write
+struct SceneArgs {
+    const float* tris;
+    const int32_t *tri_lo, *tri_hi;
+    int num_tris, num_models;
+    const float* poses;
+    const int32_t *pose_model, *pose_label;  // pose_label nullable
+    int num_poses;
+    int width, height;
+    const float* proj;
+    const int32_t* src_depth;  // the source: read only with occlude
+    const uint8_t* src_mask;
+    int occlude;
+    float occlusion_threshold;
+    unsigned long long* keys;  // H x W, all-ones before the launch
+};
+// every pose's fragments that its own source black-out keeps into a.keys (render_scene_kernel, scene_zero_kernel), then
+// the keys unpacked: rgb as launch_render_finalize's, color 3 planes of H x W; owner / color / visible nullable, visible
+// zero before the launch
+hipError_t launch_render_scene(const SceneArgs& a, hipStream_t s);
+hipError_t launch_scene_finalize(const unsigned long long* keys, int num_tris, int num_poses, int width, int height,
+                                 const uint32_t* rgb, int32_t* depth, int32_t* owner, uint8_t* color,
+                                 int32_t* visible, hipStream_t s);
 // 3-DoF world-frame bounds of depth2cloud_global (compute_point_clouds.cuh:79-91, 125-133): a pixel is
 // kept when its camera-frame point, moved to the world by m (3 x 4 row-major, camera_transform), lies
 // inside [b1, b0] x [b3, b2] x [b5, b4] (the reference's xmax, xmin, ymax, ymin, zmax, zmin, as floats).

@@ -20,7 +20,9 @@ Restates sbpl_perception/experiments/src/perch_fat.cpp:39-330 on this build's Ob
     ObjectRecognizer, 3-DoF (0, the table grid) through TabletopRecognizer.  compute_type 0 / 2 (CPU greedy ICP,
     PERCH 1.0 tree search) are outside this build's hot path (SURVEY.md section 2) and exit with status 2;
   - the master writes output_poses.txt (13 lines per detected object) and output_stats.txt (perch_fat.cpp:302-323),
-    with the GICP stage's own time (gpu_stats.icp_runtime, search_env.cpp:1715-1716) in the ICP-Time column.
+    with the GICP stage's own time (gpu_stats.icp_runtime, search_env.cpp:1715-1716) in the ICP-Time column; the
+    recognizer, whose debug directory is experiment_dir (SetDebugDir, perch_fat.cpp:116), writes cost_dump.json and the
+    greedy state's picture gpu-graph_state-0-color.png / -depth.png there (search_env.cpp:2645, 1025-1091).
 
 With torch.distributed initialised from the environment (torchrun), every rank searches its contiguous shard of the
 candidate states and only rank 0 writes (SURVEY.md 8e) -- the reference's boost::mpi ranks, as one rank per GPU.

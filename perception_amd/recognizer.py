@@ -275,8 +275,11 @@ class ObjectRecognizer:
         self.last_stats = EnvStats()
         self.last_timing: dict = {}
         # EnvObjectRecognition::debug_dir_: when set, compute_greedy_render_poses writes <debug_dir>/cost_dump.json
-        # (search_env.cpp:2463-2464, 2600-2619, 2647-2649); perch_fat sets it to the experiment directory
+        # (search_env.cpp:2463-2464, 2600-2619, 2647-2649) and the greedy state's picture, gpu-graph_state-0-color.png
+        # and -depth.png (PrintStateGPU, search_env.cpp:2645); perch_fat sets it to the experiment directory
         self.debug_dir: Optional[str] = None
+        # with debug_dir set, the last search's composed state (render_state): poses, depth, color, owner, visible
+        self.last_state: Optional[dict] = None
 
     # -- ObjectRecognizer::SetStaticInput -> LoadObjFiles (search_env.cpp:253-307) -----------------
     def set_static_input(self, model_names: Sequence[str], six_dof: bool = True):
@@ -353,6 +356,13 @@ class ObjectRecognizer:
         return valid_pose_mask(translations, seg, self._search_radius(model_id),
                                self.params.min_neighbor_points_for_valid_pose, self.device)
 
+    def _required_object(self, model_id: int) -> int:
+        """A model's required object id: its place among the segmented objects (the label its states are scored
+        against), or one past them."""
+        name = self.model_names[model_id]
+        return self.segmented_object_names.index(name) if name in self.segmented_object_names else \
+            len(self.segmented_object_names)
+
     def _state_lists(self, inp: RecognitionInput):
         """Every model's pose list (poses.txt rows or inp.pose_lists) with its model id, required object id and
         IsValidPose's squared search radius as float32, concatenated in model order; None when there are none."""
@@ -367,8 +377,7 @@ class ObjectRecognizer:
                 P = np.zeros((0, 7))
             if not len(P):
                 continue
-            req = self.segmented_object_names.index(name) if name in self.segmented_object_names else \
-                len(self.segmented_object_names)
+            req = self._required_object(ii)
             rad = self._search_radius(ii)
             Ps.append(P)
             models.append(np.full(len(P), ii, np.int32))
@@ -656,6 +665,10 @@ class ObjectRecognizer:
             dump = bool(flag.item())
         if dump:
             self._write_cost_dump(inp, n_total, lo, n, adj_all if n > 0 else None, pm if n > 0 else None, world, rank)
+        # the greedy state's picture (PrintStateGPU, search_env.cpp:2645): every rank holds the winners, rank 0 draws
+        self.last_state = None
+        if self.debug_dir is not None and rank == 0:
+            self._write_state_image(results)
         t_end = time.perf_counter()
         # host-side breakdown of the last search (seconds): successor states (poses.txt + IsValidPose), per-state
         # inputs of the GPU call, the GPU search (launch .. synchronise, incl. the exchange), results
@@ -729,6 +742,39 @@ class ObjectRecognizer:
                           "quaternion": [float(v) for v in c32[r, 3:7]],
                           "lie_rotation": [float(v) for v in lie[r]]})
         pio.write_cost_dump(os.path.join(self.debug_dir, "cost_dump.json"), poses)
+
+    # -- PrintStateGPU(greedy_state) (search_env.cpp:1718-1781, called at 2645) -------------------------
+    def render_state(self, res, occlude: bool = False):
+        """The greedy state as one frame: the winners of compute_greedy_render_poses ((model, cost, index, ContPose)
+        tuples) rendered together (PoseCore.render_scene).  Their poses are rebuilt from the ContPoses by the search's
+        own state -> pose path, as the reference rebuilds them from the object states (search_env.cpp:1535-1576), not
+        taken from the adjusted matrices.  occlude=True applies each winner's source black-out, with its label in 6-DoF
+        and by the threshold in 3-DoF; the default is the reference's (search_env.cpp:1739: no occlusion).
+        -> (poses (N, 16), depth (H, W) int32 cm, color (3, H, W) uint8, owner (H, W) int32: the row of `res` that owns
+        each pixel or -1, visible (N,) int32) on the GPU.  A LocalizationResult is taken as well."""
+        if isinstance(res, LocalizationResult):
+            res = [(self.model_names.index(n), c, i, p) for n, c, i, p in
+                   zip(res.model_names, res.costs, res.indices, res.detected_poses)]
+        model = np.array([r[0] for r in res], np.int32)
+        cont = np.array([r[3] for r in res], np.float64).reshape(-1, 7)
+        states = States(model, np.array([self._required_object(int(m)) for m in model], np.int32), cont)
+        pm = torch.from_numpy(states.model).to(self.device)
+        poses = self._state_poses_dev(torch.from_numpy(states.pose).to(self.device), pm)
+        pl = self._pose_labels(states) if occlude and len(states) else None
+        return (poses,) + self.core.render_scene(poses, pm, pl, self.params.gpu_occlusion_threshold, occlude=occlude)
+
+    def _write_state_image(self, res):
+        """<debug_dir>/gpu-graph_state-0-color.png as PrintGPUImages writes it (search_env.cpp:1025-1091: H x W x 3,
+        red, green, blue from planes 0, 1, 2) and, the line the reference has commented out (1071), the depth beside it
+        as gpu-graph_state-0-depth.png (uint16 centimetres); the arrays stay on last_state."""
+        poses, depth, color, owner, visible = self.render_state(res)
+        self.last_state = {"poses": poses.cpu().numpy(), "depth": depth.cpu().numpy(), "color": color.cpu().numpy(),
+                           "owner": owner.cpu().numpy(), "visible": visible.cpu().numpy()}
+        st = self.last_state
+        pio.save_png(os.path.join(self.debug_dir, "gpu-graph_state-0-color.png"),
+                     np.ascontiguousarray(st["color"].transpose(1, 2, 0)))
+        pio.save_png(os.path.join(self.debug_dir, "gpu-graph_state-0-depth.png"),
+                     np.clip(st["depth"], 0, 65535).astype(np.uint16))
 
     @property
     def _last_costs(self):
