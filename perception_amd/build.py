@@ -86,12 +86,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
 def build_checkers(verbose: bool = False) -> list:
     """Test-infrastructure binaries under tools/bin (not part of libpcore.so): fdiv_check compares
     pcore_fdiv.h's division against the compiler's IEEE division on the GPU (tests/test_gpu_fdiv.py), bary_check
-    the fragment test's barycentrics with and without the reference's halves (tests/test_gpu_fragment_nohalf.py)."""
+    the fragment test's barycentrics with and without the reference's halves (tests/test_gpu_fragment_nohalf.py),
+    recip_check the interior pose's area reciprocal against 1.0f / Y (tests/test_gpu_recip_interior.py)."""
     root = os.path.dirname(HERE)
     out_dir = os.path.join(root, "tools", "bin")
     os.makedirs(out_dir, exist_ok=True)
     built = []
-    for name in ("fdiv_check", "bary_check"):
+    for name in ("fdiv_check", "bary_check", "recip_check"):
         src = os.path.join(root, "tools", name + ".hip")
         out = os.path.join(out_dir, name)
         cmd = [hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", src,

@@ -23,10 +23,16 @@
 
 namespace pcore {
 
-__device__ __forceinline__ float recip_refined(float b) {
+// r0: the raw v_rcp_f32(b) the refinement starts from
+__device__ __forceinline__ float recip_refined(float b, float& r0) {
     const float r = __builtin_amdgcn_rcpf(b);
     const float e = __builtin_fmaf(-b, r, 1.0f);
+    r0 = r;
     return __builtin_fmaf(e, r, r);
+}
+__device__ __forceinline__ float recip_refined(float b) {
+    float r0;
+    return recip_refined(b, r0);
 }
 
 __device__ __forceinline__ float quot_refined(float a, float b, float r1) {
@@ -93,11 +99,37 @@ __device__ __forceinline__ bool absbits_range_ok(uint32_t umin, uint32_t umax) {
 //     and every sample centre (an integer), is a multiple of g = 2^-25, of magnitude below 2^56;
 //   - a coordinate difference is then a multiple of g below 2^57 (rounding keeps multiples of g), a product of two a
 //     multiple of g^2 = 2^-50 below 2^114, and X, Y -- differences of two products -- are 0 or in [2^-50, 2^115).
-// NOHALF = false is the reference's form (image_renderer.cuh:44-57, 112-121).
-template <bool NOHALF>
+// An interior pose (pose_window: fastdiv, and the proven box of every computed screen coordinate lies in
+// [0, W-1] x [0, H-1], W, H <= 2^14) tightens this: every screen coordinate is a multiple of g in [0, 2^14), a
+// difference of two a multiple of g of magnitude below 2^14, a product of two differences a multiple of g^2 below
+// 2^28, and Y is 0 or has 2^-50 <= |Y| < 2^29 (biased exponent in [77, 155]).  For 1.0f / Y with such a Y
+// v_div_scale scales neither operand and leaves VCC = 0 (exponent difference 127 - e(Y) in [-28, 50], far inside
+// +-96; Y, 1 / Y in (2^-29, 2^50] and the numerator all normal, the numerator's exponent 127 > 23), v_div_fmas is a
+// plain fma and v_div_fixup passes its result through, so the compiler's sequence less its no-op steps -- and less
+// the product 1.0 * r1, which is r1 -- gives the same bits: recip_interior below, 7 instructions.  For Y = +-0 the
+// division's v_div_fixup returns the infinity of Y's sign, which is the raw v_rcp_f32(Y); the refined steps would give
+// NaN there (0 * inf), and NaN barycentrics pass the inside test where infinite ones can fail it, so the select
+// matters.  tools/recip_check.hip compares the two over every float of that range, both signs, and +-0.
+// BARY: 0 the reference's form (image_renderer.cuh:44-57, 112-121), 1 without the halves, 2 without the halves and
+// with the interior pose's reciprocal.
+__device__ __forceinline__ float recip_interior(float Y) {
+    float r0;
+    const float r1 = recip_refined(Y, r0);
+    const float e1 = __builtin_fmaf(-Y, r1, 1.0f);  // quot_refined(1, Y, r1) with q0 = 1 * r1 = r1
+    const float q1 = __builtin_fmaf(e1, r1, r1);
+    const float e2 = __builtin_fmaf(-Y, q1, 1.0f);
+    const float q = __builtin_fmaf(e2, r1, q1);
+    return Y == 0.0f ? r0 : q;
+}
+
+template <int BARY>
 __device__ __forceinline__ void frag_barycentrics(float A0, float A1, float B0, float B1, float C0, float C1, float P0,
                                                   float P1, float& beta, float& gamma) {
-    if constexpr (NOHALF) {
+    if constexpr (BARY == 2) {
+        const float base_inv = recip_interior((C0 - A0) * (B1 - A1) - (B0 - A0) * (C1 - A1));
+        beta = ((C0 - A0) * (P1 - A1) - (P0 - A0) * (C1 - A1)) * base_inv;
+        gamma = ((P0 - A0) * (B1 - A1) - (B0 - A0) * (P1 - A1)) * base_inv;
+    } else if constexpr (BARY == 1) {
         const float base_inv = 1.0f / ((C0 - A0) * (B1 - A1) - (B0 - A0) * (C1 - A1));
         beta = ((C0 - A0) * (P1 - A1) - (P0 - A0) * (C1 - A1)) * base_inv;
         gamma = ((P0 - A0) * (B1 - A1) - (B0 - A0) * (P1 - A1)) * base_inv;
@@ -145,6 +177,28 @@ __device__ __forceinline__ int32_t frag_depth_certified(float alpha, float beta,
     }
     if (active && (!z_ok || num != num || d != dh)) {
         asm volatile("");
+        d = frag_depth_ieee(alpha, beta, gamma, z0, z1, z2);
+    }
+    return d;
+}
+
+// frag_depth_certified(..., z_known_ok = true) from the reciprocal depths rz_i = v_rcp_f32(z_i) the caller computed
+// once per vertex: the certified chain uses a vertex depth only as v_rcp_f32(z_i) -- the same instruction on the
+// same input, so the same bits wherever it is issued -- and the depths themselves only in the IEEE fallback, for which
+// exact_z(z0, z1, z2) fetches them inside the exec-masked branch.
+template <class ExactZ>
+__device__ __forceinline__ int32_t frag_depth_certified_rz(float alpha, float beta, float gamma, float rz0, float rz1,
+                                                           float rz2, bool active, ExactZ&& exact_z) {
+    const float num = alpha + beta + gamma;
+    const float oxa = alpha * rz0, oya = beta * rz1, oza = gamma * rz2;
+    const float f = num * __builtin_amdgcn_rcpf(oxa + oya + oza);
+    const float e = fabsf(f) * 0x1p-19f;
+    int32_t d = cvt_i32_rz_sat((f - e) + 0.5f);
+    const int32_t dh = cvt_i32_rz_sat((f + e) + 0.5f);
+    if (active && (num != num || d != dh)) {
+        asm volatile("");
+        float z0, z1, z2;
+        exact_z(z0, z1, z2);
         d = frag_depth_ieee(alpha, beta, gamma, z0, z1, z2);
     }
     return d;

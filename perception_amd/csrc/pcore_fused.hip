@@ -34,7 +34,7 @@ constexpr int kRecStride = kRecCap + 2;
 constexpr int kSmallK = 4;    // triangles touching <= kSmallK samples are queued; larger ones are
                               // processed cooperatively by the whole wave
 
-struct TriRec {  // a triangle in registers: screen-space vertices, camera z
+struct TriRec {  // a triangle in registers: screen-space vertices, camera z (or its reciprocal: raster_sample, RZ)
     float a0, a1, b0, b1, c0, c1, z0, z1, z2;
 };
 // A queued (triangle, sample) pair in the LDS record ring (8 bytes): x = the triangle's slot word (its three
@@ -69,12 +69,13 @@ __device__ __forceinline__ int sample_window(const float (&bmin)[2], const float
 struct FusedSmem {
     int32_t* zbuf;  // tile samples
     float2* vxy;    // kWaves * kVRing * 64: screen (x, y) of the wave's vertex ring
-    float* vz;      // kWaves * kVRing * 64: camera z (cm)
+    float* vz;      // kWaves * kVRing * 64: camera z (cm); v_rcp_f32 of it in the depth pass of a fastdiv pose
     uint2* vbd;     // kWaves * 2 * 64: packed int16 sample-window bounds of the last two passes
     uint2* ring;    // kWaves * kRecStride queued triangle records (phase 1); int32 point queues in phase 2
     uint32_t* ring_id;  // kWaves * kRecStride original triangle ids (colour id pass only)
     uint32_t* bitmap;
-    int32_t* counters;  // [0] bad, [1] explained, [2] points; [4..9] the pose window (x0, y0, nx, ny, fastdiv, sparse)
+    int32_t* counters;  // [0] bad, [1] explained, [2] points; [4..10] the pose window (x0, y0, nx, ny, fastdiv, sparse,
+                        // interior)
 };
 constexpr int kRingSlots = kVRing * kWave;
 static_assert(kRingSlots <= (1 << kRingSlotBits), "vertex ring slots must fit the 9-bit triangle indices");
@@ -91,19 +92,28 @@ struct SampleWin {
     // the vertex stage may skip the projection's zero entries (raster_phase): a.proj_sparse, every model vertex
     // finite and the camera rows' bounds over the model's box far from FLT_MAX
     int sparse;
+    // a fastdiv pose whose proven box of computed screen coordinates (pose_window) lies inside the image, [0, W-1] x
+    // [0, H-1]: the vertex pass needs no clamp to the image (vertex_bounds) and the fragment test's area reciprocal
+    // no scaling steps (pcore_fdiv.h, recip_interior).  A property of the pose: a chunk keeps its window's flag.
+    int interior;
 };
 
 // IDPASS = false: depth pass (atomicMin of the fragment depth).  IDPASS = true: colour id pass over the
 // final depths: the fragments whose depth equals the sample's minimum leave the lowest original triangle
 // index -- the colour the reference's serial z-test (strict <) keeps.
-template <bool IDPASS = false, bool NOHALF = false>
+// RZ: r.z0, r.z1, r.z2 hold the reciprocal depths v_rcp_f32(z) and exact_z(z0, z1, z2) fetches the depths for the
+// lanes of the fragment depth's IEEE fallback (the depth pass of a fastdiv pose, raster_phase)
+template <bool IDPASS = false, int BARY = 0, bool RZ = false, class ExactZ>
 __device__ __forceinline__ void raster_sample(const TriRec& r, int kx, int ky, int s, int H, const SampleWin& w,
-                                              int32_t* zbuf, int32_t* cid = nullptr, uint32_t id = 0) {
+                                              int32_t* zbuf, int32_t* cid, uint32_t id, ExactZ&& exact_z) {
     const float P0 = (float)(kx * s);
     const float P1 = (float)(H - 1 - ky * s);
     int32_t d;
-    const bool in = fragment<NOHALF>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d,
-                                     w.fastdiv != 0);
+    bool in;
+    if constexpr (RZ)
+        in = fragment_rz<BARY>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d, exact_z);
+    else
+        in = fragment<BARY>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d, w.fastdiv != 0);
     const int k = (int)__umul24((uint32_t)(ky - w.y0), (uint32_t)w.nx) + (kx - w.x0);  // inside the window
     if constexpr (IDPASS) {
         if (in && d == zbuf[k]) atomicMin(&cid[k], (int32_t)id);
@@ -123,7 +133,7 @@ size_t fused_lds_bytes(int tile_samples, int bitmap_words, bool colour) {
     b += al((size_t)kWaves * kRecStride * 8);
     if (colour) b += al((size_t)kWaves * kRecStride * 4);
     b += al((size_t)bitmap_words * 4);
-    b += 48;  // counters: [0] bad, [1] explained, [2] points; [4..9] the pose window (fused_cost_kernel)
+    b += 48;  // counters: [0] bad, [1] explained, [2] points; [4..10] the pose window (fused_cost_kernel)
     return b;
 }
 
@@ -183,7 +193,11 @@ typedef short short2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ short2v as_s2(uint32_t v) { return __builtin_bit_cast(short2v, v); }
 constexpr uint32_t kNanBounds = 0x80008000u;
 
-template <int STRIDE>
+// INTERIOR: the vertex of an interior pose (SampleWin::interior), without the four clamps.  pose_window proves
+// 0 <= xlo <= sx <= xhi <= W-1 = cmax0 for the computed sx of every vertex, so v_med3(sx, 0, 65536) = sx (0 <= sx <=
+// 16383 < 65536) and v_med3(sx, -65536, cmax0) = sx (-65536 < sx <= cmax0); the same for sy with H-1 = cmax1.  (A sum
+// sx = t + W/2 that is zero is +0 under round-to-nearest, and both conversions take either zero to 0.)
+template <int STRIDE, bool INTERIOR = false>
 __device__ __forceinline__ uint2 vertex_bounds(float sx, float sy, int s, float cmax0, float cmax1, int H,
                                               bool finite = false) {
     if (!finite && __builtin_isunordered(sx, sy)) return make_uint2(kNanBounds, 0u);
@@ -191,10 +205,18 @@ __device__ __forceinline__ uint2 vertex_bounds(float sx, float sy, int s, float 
     // sx, sy are not NaN here, so each clamp is one v_med3_f32, and the clamped values are small enough
     // (|v| <= 65536 < 2^23) that v + 0.5 is exact: trunc(v + 0.5) = floor(v + 0.5) for v >= 0 is one
     // v_cvt_rpi_i32_f32, floor(v) one v_cvt_flr_i32_f32 (cvt_rpi / cvt_flr below)
-    const int lo0 = cvt_rpi(__builtin_amdgcn_fmed3f(sx, 0.0f, 65536.0f));
-    const int lo1 = cvt_rpi(__builtin_amdgcn_fmed3f(sy, 0.0f, 65536.0f));
-    const int hi0 = cvt_flr(__builtin_amdgcn_fmed3f(sx, -65536.0f, cmax0));
-    const int hi1 = cvt_flr(__builtin_amdgcn_fmed3f(sy, -65536.0f, cmax1));
+    int lo0, lo1, hi0, hi1;
+    if constexpr (INTERIOR) {
+        lo0 = cvt_rpi(sx);
+        lo1 = cvt_rpi(sy);
+        hi0 = cvt_flr(sx);
+        hi1 = cvt_flr(sy);
+    } else {
+        lo0 = cvt_rpi(__builtin_amdgcn_fmed3f(sx, 0.0f, 65536.0f));
+        lo1 = cvt_rpi(__builtin_amdgcn_fmed3f(sy, 0.0f, 65536.0f));
+        hi0 = cvt_flr(__builtin_amdgcn_fmed3f(sx, -65536.0f, cmax0));
+        hi1 = cvt_flr(__builtin_amdgcn_fmed3f(sy, -65536.0f, cmax1));
+    }
     int A0 = floor_div<STRIDE>(lo0 + ss - 1, s), A1 = floor_div<STRIDE>(hi0, s);
     int B0 = floor_div<STRIDE>(H - 1 - hi1 + ss - 1, s), B1 = floor_div<STRIDE>(H - 1 - lo1, s);
     if constexpr (STRIDE == 0) {
@@ -207,15 +229,24 @@ __device__ __forceinline__ uint2 vertex_bounds(float sx, float sy, int s, float 
 }
 
 
-// FD: the pose's fastdiv flag known at compile time (0 / 1; the depth pass instantiates both and picks one per pose, so
-// a fastdiv pose's steps carry no NaN-triangle test or range checks at all), or -1 to read it from the window
+// FD: the pose's class known at compile time (0: general, 1: fastdiv, 2: fastdiv and interior; the depth pass
+// instantiates the three and picks one per pose, so a fastdiv pose's steps carry no NaN-triangle test or range checks at
+// all, and an interior pose's no clamp of its vertices to the image and no scaling steps in the area's reciprocal), or
+// -1 to read the fastdiv flag from the window (the colour id pass: the general fragment test and clamps)
 template <int STRIDE, bool IDPASS = false, int FD = -1>
 __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem& sm, int pose, const SampleWin& sw_in,
                                              int32_t* cid, FProf& fp) {
     SampleWin sw = sw_in;
-    if constexpr (FD >= 0) sw.fastdiv = FD;
-    // the fragment test without its halves: the depth pass of a fastdiv pose only (pcore_fdiv.h)
-    constexpr bool kNoHalf = FD == 1 && !IDPASS;
+    if constexpr (FD >= 0) sw.fastdiv = FD >= 1;
+    // the fragment test without its halves: the depth pass of a fastdiv pose only; with the unscaled area reciprocal:
+    // of an interior pose only (pcore_fdiv.h)
+    constexpr int kBary = IDPASS || FD < 1 ? 0 : FD;
+    constexpr bool kInterior = FD == 2 && !IDPASS;
+    // The vertex ring keeps v_rcp_f32(z) instead of z: the depth pass of a fastdiv pose.  There the fragment test uses a
+    // vertex depth only as v_rcp_f32(z) -- which the vertex pass issues anyway, as the first step of its refined
+    // reciprocal -- except in the certified depth's rare IEEE fallback, whose lanes compute z again from the stream
+    // (ring_z below).
+    constexpr bool kRz = FD >= 1 && !IDPASS;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: scalar loads of stream headers
     const int lane = tid & 63;
@@ -252,6 +283,22 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
     // i mod kRecCap.  Full 64-record batches are flushed as soon as they exist; a partial batch only when a
     // vertex pass would overwrite vertices a pending record may reference, at a stream switch and at the end.
     int rec_total = 0, rec_done = 0;
+    // kRz: the stream whose vertices the ring holds -- its first vertex pass and how many of its passes are written.
+    // Set after the flush at a stream switch (which still serves the previous stream's records) and kept past the last
+    // stream for the final flush.
+    int ring_first = 0, ring_passes = 0;
+    // The camera z of the vertex in a ring slot (buffer * 64 + lane), for the fallback lanes.
+    // A pending record's slot has not been overwritten (the flush rules of the ring), so it holds the latest written
+    // pass p of the stream with p mod kVRing == buffer; that pass is sverts[(ring_first + p) * 64 ..], and z is the
+    // vertex pass's own row4 on it (contraction off: the same bits).  0 <= p < ring_passes, so the read lies within
+    // the passes this wave has already loaded from its stream, [ring_first, ring_first + ring_passes) * 64; the clamp to
+    // pass 0 keeps it there even for a slot no pass has written, which no record names.
+    auto ring_z = [&](uint32_t slot) {
+        const int last = ring_passes - 1, d = last - (int)(slot >> 6);
+        const int p = d >= 0 ? last - d % kVRing : 0;
+        const float* v = reinterpret_cast<const float*>(a.sverts + (size_t)(ring_first + p) * kStepSlots + (slot & 63u));
+        return row4(m20, m21, m22, m23, v[0], v[1], v[2]);
+    };
 
     const int dbg = dbg_skip_bits(a);  // the ablation mask: the constant 0 in the production build
     FlushStats fs;
@@ -277,8 +324,12 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                     asm volatile("" : "+v"(r.z0), "+v"(r.z1), "+v"(r.z2));
                     // one record per (triangle, sample): the sample is rec.y = kx | ky << 16
                     fs.record();
-                    raster_sample<IDPASS, kNoHalf>(r, (int)(rec.y & 0xffffu), (int)(rec.y >> 16), s, H, sw, sm.zbuf,
-                                                   cid, id);
+                    raster_sample<IDPASS, kBary, kRz>(r, (int)(rec.y & 0xffffu), (int)(rec.y >> 16), s, H, sw, sm.zbuf,
+                                                      cid, id, [&](float& z0, float& z1, float& z2) {
+                                                          z0 = ring_z(rec.x & 511u);
+                                                          z1 = ring_z((rec.x >> 9) & 511u);
+                                                          z2 = ring_z((rec.x >> 18) & 511u);
+                                                      });
                 }
             }
         }
@@ -296,6 +347,8 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
             fs.partial_flush(lane);
             flush(rec_total - rec_done);
         }
+        ring_first = sd.z;
+        ring_passes = 0;
         // hist[k]: rec_total when pass P-1-k was written (P = the next pass).  A batch issued after pass h
         // references passes >= h - kRefPasses + 1, so before pass P overwrites the buffer of pass P - kVRing every
         // record appended before pass P - (kVRing - kRefPasses) was written must be flushed.
@@ -353,7 +406,8 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                     // fastdiv bound (1 <= lz < 2^41, |px|, |py| < 2^41) the only operand out of range is a numerator
                     // below 2^-40, whose quotient (IEEE or unscaled) is below 2^-40: q * W/2 + W/2 rounds to W/2 either
                     // way, so no per-vertex check is needed.
-                    const float r1 = recip_refined(lz);
+                    float r0;  // v_rcp_f32(lz)
+                    const float r1 = recip_refined(lz, r0);
                     float qx = quot_refined(px, lz, r1), qy = quot_refined(py, lz, r1);
                     float sx = qx * hw + hw, sy = qy * hh + hh;
                     if (!sw.fastdiv) {
@@ -367,11 +421,12 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                         }
                     }
                     vxy[buf * kWave + lane] = make_float2(sx, sy);
-                    vz[buf * kWave + lane] = lz;
+                    vz[buf * kWave + lane] = kRz ? r0 : lz;
                     // a wave-uniform branch, so a fastdiv pose's pass carries no NaN test, default bounds or exec
                     // masking (the screen coordinates are finite there)
                     uint2 vb;
-                    if (sw.fastdiv) vb = vertex_bounds<STRIDE>(sx, sy, s, cmax0, cmax1, H, true);
+                    if constexpr (kInterior) vb = vertex_bounds<STRIDE, true>(sx, sy, s, cmax0, cmax1, H, true);
+                    else if (sw.fastdiv) vb = vertex_bounds<STRIDE>(sx, sy, s, cmax0, cmax1, H, true);
                     else vb = vertex_bounds<STRIDE>(sx, sy, s, cmax0, cmax1, H, false);
                     vbd[(buf & 1) * kWave + lane] = vb;
                 }
@@ -379,6 +434,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                 for (int k = kVRing - kRefPasses - 1; k > 0; k--) hist[k] = hist[k - 1];
                 hist[0] = rec_total;
                 buf = buf + 1 == kVRing ? 0 : buf + 1;
+                ring_passes++;
                 fs.vertex_pass(lane);
                 wave_sync();
             }
@@ -490,13 +546,19 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                             const int bnx = (int)((uint32_t)__builtin_amdgcn_readlane((int)nxy, j) & 0xffffu);
                             const int bnk = __builtin_amdgcn_readlane(nk, j);
                             const uint32_t bid = IDPASS ? (uint32_t)__builtin_amdgcn_readlane((int)cidt, j) : 0u;
+                            const uint32_t bct = kRz ? (uint32_t)__builtin_amdgcn_readlane((int)ct, j) : 0u;
                             // q / bnx without an integer division: the float quotient is within 1e-3 of q / bnx (q / bnx
                             // is at most the sample rows), so one correction step gives the exact row
                             const float inv_nx = 1.0f / (float)bnx;
                             for (int q = lane; q < bnk; q += kWave) {
                                 int iy = (int)(((float)q + 0.5f) * inv_nx), ix = q - iy * bnx;
                                 if (ix < 0) { iy--; ix += bnx; } else if (ix >= bnx) { iy++; ix -= bnx; }
-                                raster_sample<IDPASS, kNoHalf>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid);
+                                raster_sample<IDPASS, kBary, kRz>(rb, bkx0 + ix, bky0 + iy, s, H, sw, sm.zbuf, cid, bid,
+                                                                  [&](float& z0, float& z1, float& z2) {
+                                                                      z0 = ring_z(bct & 511u);
+                                                                      z1 = ring_z((bct >> 9) & 511u);
+                                                                      z2 = ring_z((bct >> 18) & 511u);
+                                                                  });
                             }
                         } while (big);
                     }
@@ -549,7 +611,8 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
 // bounds of vertex_window (every triangle window lies inside).  The whole sampled image when the box is
 // not finite or comes within 5 % of its depth magnitude of the camera plane.  Wave-uniform; every wave of
 // the workgroup computes the same window.
-__device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)[12], int s) {
+// Always inline: a call would make the kernel keep its argument block in scratch memory to pass the reference.
+__device__ __forceinline__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)[12], int s) {
     const float4 lo = a.model_box[2 * model], hi = a.model_box[2 * model + 1];
     // magnitude of the terms of each camera row over the box (bounds the rounding of any vertex's row)
     const float ax = fmaxf(fabsf(lo.x), fabsf(hi.x)), ay = fmaxf(fabsf(lo.y), fabsf(hi.y));
@@ -558,7 +621,7 @@ __device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)
     const float By = fabsf(m[4]) * ax + fabsf(m[5]) * ay + fabsf(m[6]) * az + fabsf(m[7]);
     const float Bz = fabsf(m[8]) * ax + fabsf(m[9]) * ay + fabsf(m[10]) * az + fabsf(m[11]);
     const int sparse = (a.proj_sparse && lo.w != 0.0f && Bx < 1.0e30f && By < 1.0e30f) ? 1 : 0;  // NaN bounds fail
-    const SampleWin whole = {0, 0, a.ws, a.hs, 0, sparse};
+    const SampleWin whole = {0, 0, a.ws, a.hs, 0, sparse, 0};
     const int c = lane_id() & 7;
     const float x = (c & 1) ? hi.x : lo.x, y = (c & 2) ? hi.y : lo.y, z = (c & 4) ? hi.z : lo.z;
     const float Wf = (float)a.width, Hf = (float)a.height;
@@ -599,7 +662,10 @@ __device__ SampleWin pose_window(const FusedArgs& a, int model, const float (&m)
     // (<= 6 eps Bz); the margin 1e-5 Bz covers that.  |x|, |y| after the projection are below Pbx, Pby.
     // (The fragment test of a fastdiv pose relies on these bounds too: pcore_fdiv.h, frag_barycentrics.)
     const bool fastdiv = lzmin - 1.0e-5f * Bz >= 1.0f && Bz < 0x1p40f && Pbx < 0x1p40f && Pby < 0x1p40f;
-    return SampleWin{X0, Y0, max(0, X1 - X0 + 1), max(0, Y1 - Y0 + 1), fastdiv ? 1 : 0, sparse};
+    // interior: the box [xlo, xhi] x [ylo, yhi] holds every vertex's computed screen coordinates (it is what the window
+    // above is made from) and lies inside the image; NaN bounds fail
+    const bool interior = fastdiv && xlo >= 0.0f && xhi <= Wf - 1.0f && ylo >= 0.0f && yhi <= Hf - 1.0f;
+    return SampleWin{X0, Y0, max(0, X1 - X0 + 1), max(0, Y1 - Y0 + 1), fastdiv ? 1 : 0, sparse, interior ? 1 : 0};
 }
 
 
@@ -633,7 +699,8 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
     auto chunk = [&](const SampleWin& sw) __attribute__((always_inline)) {
         const int tn = sw.nx * sw.ny;  // samples of the chunk (tile)
         for (int i = tid; i < tn; i += kThreads) sm.zbuf[i] = INT_MAX;
-        if (sw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, sw, nullptr, fp);
+        if (sw.interior) raster_phase<STRIDE, false, 2>(a, sm, pose, sw, nullptr, fp);
+        else if (sw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, sw, nullptr, fp);
         else raster_phase<STRIDE, false, 0>(a, sm, pose, sw, nullptr, fp);
         fp.mark(2);
         __syncthreads();
@@ -802,7 +869,7 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
             for (int c0 = 0; c0 < pw.nx; c0 += cw) {
                 if (r0 > 0 || c0 > 0) __syncthreads();  // the previous chunk's points are processed
                 chunk(SampleWin{pw.x0 + c0, pw.y0 + r0, min(cw, pw.nx - c0), min(ch, pw.ny - r0), pw.fastdiv,
-                                pw.sparse});
+                                pw.sparse, pw.interior});
             }
     }
     // per-wave totals
@@ -873,7 +940,7 @@ fused_cost_kernel(FusedArgs a) {
     // the pose window, by wave 0 only (every wave would compute the same one), shared through LDS
     if (threadIdx.x < kWave) {
         const int model = a.pose_model[pose];
-        SampleWin w = {0, 0, 0, 0, 0, 0};  // invalid model: nothing is rendered
+        SampleWin w = {0, 0, 0, 0, 0, 0, 0};  // invalid model: nothing is rendered
         if (model >= 0 && model < a.num_models) {
             float m[12];
             load_pose_rows(a.poses, pose, m);
@@ -886,13 +953,15 @@ fused_cost_kernel(FusedArgs a) {
             sm.counters[7] = w.ny;
             sm.counters[8] = w.fastdiv;
             sm.counters[9] = w.sparse;
+            sm.counters[10] = w.interior;
         }
     }
     __syncthreads();
     const SampleWin sw = {__builtin_amdgcn_readfirstlane(sm.counters[4]), __builtin_amdgcn_readfirstlane(sm.counters[5]),
                           __builtin_amdgcn_readfirstlane(sm.counters[6]), __builtin_amdgcn_readfirstlane(sm.counters[7]),
                           __builtin_amdgcn_readfirstlane(sm.counters[8]),
-                          __builtin_amdgcn_readfirstlane(sm.counters[9])};
+                          __builtin_amdgcn_readfirstlane(sm.counters[9]),
+                          __builtin_amdgcn_readfirstlane(sm.counters[10])};
     const int tn = sw.nx * sw.ny;
     // Tile feedback, double-buffered by launch parity: every workgroup counts its window into this launch's
     // histogram (and, when chunked, the chunked-pose count) with atomics whose result it does not wait for;
@@ -963,8 +1032,10 @@ hipError_t launch_window_probe(const FusedArgs& a, int32_t* hist, hipStream_t s)
 
 // Stage CLOUD into per-pose scratch slots (the GICP source clouds): sampled raster, source occlusion,
 // then the reference's compaction order (row-major samples, compute_point_clouds.cuh:290-346).
+// (the fused kernel's register budget: with the fallback's vertex fetch the compiler otherwise takes 86 VGPRs, 5 waves)
 template <int STRIDE>
-__global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PCORE_FUSED_WAVES_PER_EU)))
+render_cloud_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int wsum[kWaves];
     __shared__ int carry_s;
@@ -975,7 +1046,7 @@ __global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
     const int cap = a.tcap > 0 && a.tcap < nsamp ? a.tcap : nsamp;  // the LDS tile (samples)
     const FusedSmem sm = carve_smem(smem_raw, cap, 0);
     const int model = a.pose_model[pose];
-    SampleWin sw = {0, 0, 0, 0, 0, 0};
+    SampleWin sw = {0, 0, 0, 0, 0, 0, 0};
     if (model >= 0 && model < a.num_models) {
         float m[12];
         load_pose_rows(a.poses, pose, m);
@@ -992,7 +1063,8 @@ __global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
     auto chunk = [&](const SampleWin& cw) __attribute__((always_inline)) {
         const int tn = cw.nx * cw.ny;
         for (int i = tid; i < tn; i += kThreads) sm.zbuf[i] = INT_MAX;
-        if (cw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, cw, nullptr, fp);
+        if (cw.interior) raster_phase<STRIDE, false, 2>(a, sm, pose, cw, nullptr, fp);
+        else if (cw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, cw, nullptr, fp);
         else raster_phase<STRIDE, false, 0>(a, sm, pose, cw, nullptr, fp);
         __syncthreads();
         const float inv_nx = tn > 0 ? 1.0f / (float)cw.nx : 0.0f;
@@ -1038,7 +1110,7 @@ __global__ void __launch_bounds__(kThreads) render_cloud_kernel(FusedArgs a) {
         for (int r0 = 0; r0 < sw.ny; r0 += ch)
             for (int c0 = 0; c0 < sw.nx; c0 += cw)
                 chunk(SampleWin{sw.x0 + c0, sw.y0 + r0, min(cw, sw.nx - c0), min(ch, sw.ny - r0), sw.fastdiv,
-                                sw.sparse});
+                                sw.sparse, sw.interior});
     }
     if (tid == 0) a.cloud_count[pose] = carry_s < a.cloud_cap ? carry_s : a.cloud_cap;
 }

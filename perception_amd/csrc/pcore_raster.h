@@ -85,14 +85,15 @@ __device__ __forceinline__ bool loop_bounds(float bmin, float bmax, int& lo, int
 // Returns whether the pixel is inside (NaN barycentrics count as inside, as in the reference) and sets the depth
 // for inside pixels; every lane runs the same instructions (no branch on the inside test), so a batch of
 // fragment tests is one straight-line block plus the depth's rare IEEE fallback.
-// NOHALF: the barycentrics without the reference's three multiplications by 0.5, bit-identical under the bound of a
-// fastdiv pose (pcore_fdiv.h); only the depth pass of a fastdiv pose asks for it.
-template <bool NOHALF = false>
-__device__ __forceinline__ bool fragment(float A0, float A1, float B0, float B1, float C0, float C1, float z0,
-                                         float z1, float z2, float P0, float P1, int32_t& depth, bool z_ok = false) {
-    float beta, gamma;
-    frag_barycentrics<NOHALF>(A0, A1, B0, B1, C0, C1, P0, P1, beta, gamma);
-    const float alpha = 1.0f - beta - gamma;
+// BARY = 1: the barycentrics without the reference's three multiplications by 0.5, bit-identical under the bound of a
+// fastdiv pose (pcore_fdiv.h); only the depth pass of a fastdiv pose asks for it.  BARY = 2: also the area's
+// reciprocal without the division's scaling steps, bit-identical under the bound of an interior pose (pcore_fdiv.h,
+// recip_interior); only the depth pass of an interior pose asks for it.
+template <int BARY = 0>
+__device__ __forceinline__ bool fragment_inside(float A0, float A1, float B0, float B1, float C0, float C1, float P0,
+                                                float P1, float& alpha, float& beta, float& gamma) {
+    frag_barycentrics<BARY>(A0, A1, B0, B1, C0, C1, P0, P1, beta, gamma);
+    alpha = 1.0f - beta - gamma;
     // !(alpha < -0 || beta < -0 || gamma < -0 || alpha > 1 || beta > 1 || gamma > 1) as one v_min3 / v_max3 each:
     // the three are arithmetic results (quiet NaNs at most), on which v_min3 / v_max3 follow IEEE minNum / maxNum
     // -- a NaN operand is skipped, as in the comparisons, and an all-NaN triple gives NaN (inside, as in the
@@ -100,10 +101,28 @@ __device__ __forceinline__ bool fragment(float A0, float A1, float B0, float B1,
     float mn, mx;
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(mn) : "v"(alpha), "v"(beta), "v"(gamma));
     asm("v_max3_f32 %0, %1, %2, %3" : "=v"(mx) : "v"(alpha), "v"(beta), "v"(gamma));
-    const bool inside = !(mn < -0.0f) && !(mx > 1.0f);
+    return !(mn < -0.0f) && !(mx > 1.0f);
+}
+template <int BARY = 0>
+__device__ __forceinline__ bool fragment(float A0, float A1, float B0, float B1, float C0, float C1, float z0,
+                                         float z1, float z2, float P0, float P1, int32_t& depth, bool z_ok = false) {
+    float alpha, beta, gamma;
+    const bool inside = fragment_inside<BARY>(A0, A1, B0, B1, C0, C1, P0, P1, alpha, beta, gamma);
     // the depth quotient chain through reciprocal estimates with an error certificate, the IEEE divisions only
     // where the certificate fails (pcore_fdiv.h, frag_depth_certified); outside lanes never take the fallback
     depth = frag_depth_certified(alpha, beta, gamma, z0, z1, z2, z_ok, inside);
+    return inside;
+}
+// The same with the vertices' reciprocal depths rz_i = v_rcp_f32(z_i) in place of the depths (a fastdiv pose's depth
+// pass: every z_i in [1, 2^41)); exact_z(z0, z1, z2) fetches the depths themselves for the lanes that take the IEEE
+// fallback (pcore_fdiv.h, frag_depth_certified_rz).
+template <int BARY, class ExactZ>
+__device__ __forceinline__ bool fragment_rz(float A0, float A1, float B0, float B1, float C0, float C1, float rz0,
+                                            float rz1, float rz2, float P0, float P1, int32_t& depth,
+                                            ExactZ&& exact_z) {
+    float alpha, beta, gamma;
+    const bool inside = fragment_inside<BARY>(A0, A1, B0, B1, C0, C1, P0, P1, alpha, beta, gamma);
+    depth = frag_depth_certified_rz(alpha, beta, gamma, rz0, rz1, rz2, inside, exact_z);
     return inside;
 }
 
