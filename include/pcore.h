@@ -339,6 +339,36 @@ int pcore_render_scene(pcore_ctx* ctx, const float* d_poses, const int32_t* d_po
                        int32_t num_poses, int32_t occlude, float occlusion_threshold, int32_t* d_out_depth,
                        uint8_t* d_out_color, int32_t* d_out_owner, int32_t* d_out_visible, pcore_stream stream);
 
+/* Stage COST of composed states (no reference counterpart: PERCH's objective is a cost of the whole state, which the
+ * reference's greedy GPU path dropped; DESIGN.md section 2, "State cost").  d_zs holds num_poses sampled z-buffers after
+ * source occlusion, exactly what pcore_evaluate writes to d_dbg_zs (hs x ws int32 each; 0 = nothing of this pose here).
+ * State s is the member list d_state_member[d_state_off[s] .. d_state_off[s + 1]) of indices into them.  Per sample the
+ * minimum non-zero depth over the members wins and the lowest list position attaining it owns the sample; owned samples
+ * of positive depth are the state's points (a negative minimum hides what is behind it and yields no point).  Each point
+ * is unprojected as pcore_evaluate does and matched with the exact 1-NN (ties to the lowest index) against the observed
+ * segment of d_pose_label[owner] -- an empty one for a label outside the segments -- or, for cost_type 0, against the
+ * whole cloud (d_pose_label is then ignored and may be NULL); it is bad when d^2 > r^2.
+ *   d_out_member_vis / _bad   num_members int32 each (nullable): the points / bad points every list entry owns
+ *   d_out_rc / _oc / _diff    num_states floats each, pcore_evaluate's formulas over num = sum vis, bad = sum bad, expl =
+ *                             the DISTINCT observed points that are the neighbour of a non-bad point of any member, and
+ *                             tot = d_state_obs_total[s]; oc and diff are written as 0 when calc_obs_cost == 0
+ * A one-member state with tot = pose_obs_total equals pcore_evaluate's costs of that pose bit for bit.  A member outside
+ * [0, num_poses) contributes nothing; a duplicate member never owns a sample; a state without members has rc = -1; a
+ * span that is not positive, or that leaves [0, num_members], is an empty state.  Spans of different states that overlap
+ * leave the member outputs of the shared entries undefined (the states' costs stay defined).  Neither the members per state nor the
+ * states are limited.  Needs a camera and an observation (PCORE_E_STATE otherwise), no meshes.  cost_type 1 and a stride
+ * that does not divide the width get PCORE_E_INVALID_ARG.  num_states == 0 is a no-op.  Asynchronous on `stream`, no host
+ * readback; every argument is checked before the first launch, and a refused call writes nothing.  While the observed
+ * cloud has at most PCORE_STATE_LDS_OBS points the explained bitmap lives in the workgroup's LDS; above, in per-context
+ * scratch that grows on first use (the growth changes pcore_generation; a capturing stream that would need it gets
+ * PCORE_E_STATE). */
+#define PCORE_STATE_LDS_OBS 131072
+int pcore_evaluate_states(pcore_ctx* ctx, const int32_t* d_zs, int32_t num_poses, const int32_t* d_pose_label,
+                          const int32_t* d_state_off, const int32_t* d_state_member, int32_t num_states,
+                          const float* d_state_obs_total, const pcore_eval_params* params, float* d_out_rc,
+                          float* d_out_oc, float* d_out_diff, int32_t* d_out_member_vis, int32_t* d_out_member_bad,
+                          int32_t num_members, pcore_stream stream);
+
 /* gpu_stats of render_cuda_multi_unified (model.h:24-27, filled at renderer.cu:1707 and 1739) for the last
  * pcore_evaluate_icp: icp_runtime = seconds of its GICP stage (source covariances + GICP launches, HIP events on
  * the call's stream -- this call waits for them); peak_memory_usage = the most device memory in use (MB,

@@ -21,6 +21,8 @@ PCORE_KEY_NONE = 0x7FFFFFFFFFFFFFFF
 # pcore_select_topk (include/pcore.h): the largest k, and the poses per partial list of a batch of at most 2^20 poses
 PCORE_TOPK_MAX = 64
 PCORE_TOPK_SLICE = 1024
+# pcore_evaluate_states (include/pcore.h): the most observed points whose explained bitmap lives in LDS
+PCORE_STATE_LDS_OBS = 131072
 
 COST_DEPTH_3DOF = 0
 COST_RGBD_3DOF = 1
@@ -37,7 +39,7 @@ EXPORTED_SYMBOLS = (
     "pcore_debug_covariances", "pcore_debug_covariances_cloud", "pcore_depth_to_cloud_ex",
     "pcore_icp_planar", "pcore_debug_planar_step",
     "pcore_scene_projective", "pcore_debug_render_clouds", "pcore_debug_colour_distance",
-    "pcore_select_topk",
+    "pcore_select_topk", "pcore_evaluate_states",
 )
 # declared in include/pcore.h too; kept apart because tests/test_abi.py's symbol pattern stops at a digit
 EXPORTED_SYMBOLS_WITH_DIGITS = ("pcore_icp_point2plane", "pcore_debug_p2p_clouds", "pcore_debug_rgb2lab",
@@ -214,6 +216,9 @@ def load(auto_build: bool = True) -> ctypes.CDLL:
     L.pcore_select.argtypes = [vp, vp, vp, vp, i32, i64, i32, vp, vp]
     if hasattr(L, "pcore_select_topk"):  # absent from older A/B builds (PCORE_LIB)
         L.pcore_select_topk.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, vp, vp]
+    if hasattr(L, "pcore_evaluate_states"):  # absent from older A/B builds (PCORE_LIB)
+        L.pcore_evaluate_states.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, ctypes.POINTER(EvalParams), vp, vp, vp,
+                                            vp, vp, i32, vp]
     L.pcore_pose_distances.argtypes =[vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.pcore_set_observation_colors.argtypes = [vp, vp, i32, vp]
     L.pcore_observed_cloud_bounded.argtypes = [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i32,

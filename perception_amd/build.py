@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpcore.so")
 SOURCES = ["pcore_fused.hip", "pcore_render.hip", "pcore_cloud.hip", "pcore_gicp.hip", "pcore_metrics.hip", "pcore_states.hip",
-           "pcore_icp2d.hip", "pcore_p2p.hip", "pcore_topk.hip", "pcore_api.hip", "pcore_api_eval.hip", "pcore_api_icp.hip"]
+           "pcore_icp2d.hip", "pcore_p2p.hip", "pcore_topk.hip", "pcore_state_cost.hip", "pcore_api.hip", "pcore_api_eval.hip", "pcore_api_icp.hip", "pcore_api_states.hip"]
 GICP_HEADERS = ["pcore_wave.h", "pcore_nn_grid.h", "pcore_gicp_scan.h", "pcore_gicp_ring.h", "pcore_gicp_probe.h"]  # pcore_gicp.hip's own
 HEADERS = GICP_HEADERS + ["pcore_internal.h", "pcore_cov.h", "pcore_gicp_math.h", "pcore_icp2d_math.h", "pcore_p2p_math.h", "pcore_dmath.h", "pcore_colour.h", "pcore_fdiv.h", "pcore_streams.h", "pcore_raster.h", "pcore_fused_probe.h", "pcore_topk.h", "pcore_ctx.h", "pcore_prep.h", os.path.join("..", "..", "include", "pcore.h")]
 ARCH = os.environ.get("PCORE_OFFLOAD_ARCH", "gfx950")

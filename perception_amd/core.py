@@ -179,6 +179,73 @@ class PoseCore:
             _ptr(df, torch.float32, "diff"), _ptr(dbg_zs, torch.int32, "dbg_zs"), _stream(stream)))
         return rc, oc, df
 
+    def evaluate_states(self, states, pose_label: Optional[torch.Tensor], state_obs_total: Optional[torch.Tensor], *,
+                        zs: Optional[torch.Tensor] = None, poses: Optional[torch.Tensor] = None,
+                        pose_model: Optional[torch.Tensor] = None, cost_type: int = _native.COST_DEPTH_6DOF,
+                        calc_obs_cost: bool = True, stride: int = 8, depth_factor: float = 100.0,
+                        sensor_resolution: float = 0.01, occlusion_threshold: float = 1.0,
+                        member_counts: bool = True, stream=None):
+        """Stage COST of composed states (pcore_evaluate_states; DESIGN.md section 2, "State cost").  `states` is a list
+        of member lists or an (off (S + 1,), member (nnz,)) pair of int32 GPU tensors; members index the poses behind
+        `zs` (N, hs, ws) int32 -- evaluate's dbg_zs -- and `pose_label` (N,).  With `poses` (N, 16) and `pose_model`
+        instead of `zs`, the poses that are a member of some state are rendered first by evaluate(..., dbg_zs=...).
+        Returns (rc, oc, diff) per state and (vis, bad) per member entry (None with member_counts=False).  Selecting
+        among states is select() with a group id per state in place of pose_model."""
+        if (zs is None) == (poses is None):
+            raise ValueError("evaluate_states: give exactly one of zs and poses")
+        dev = zs.device if zs is not None else poses.device
+        if isinstance(states, (tuple, list)) and len(states) == 2 and all(isinstance(t, torch.Tensor) for t in states):
+            off, member = states
+        else:
+            lens = [len(m) for m in states]
+            off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)).to(dev)
+            flat = np.concatenate([np.asarray(m, np.int64).reshape(-1) for m in states]) if lens else np.zeros(0)
+            member = torch.from_numpy(flat.astype(np.int32)).to(dev)
+        S, nnz = int(off.shape[0]) - 1, int(member.shape[0])
+        kw = dict(cost_type=cost_type, stride=stride, depth_factor=depth_factor,
+                  sensor_resolution=sensor_resolution, occlusion_threshold=occlusion_threshold)
+        if poses is not None:
+            if pose_model is None:
+                raise ValueError("evaluate_states: poses need pose_model")
+            n = int(poses.shape[0])
+            ok = (member >= 0) & (member < n)
+            uniq = torch.unique(member[ok].long())  # sorted: the rendered batch keeps the members' order
+            remap = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+            remap[uniq] = torch.arange(int(uniq.shape[0]), dtype=torch.int32, device=dev)
+            member = torch.where(ok, remap[member.long().clamp(0, max(n, 1) - 1)], torch.full_like(member, -1))
+            nsamp = (self.width // stride) * ((self.height + stride - 1) // stride) if stride > 0 else 0
+            zs = torch.zeros((int(uniq.shape[0]), max(nsamp, 1)), dtype=torch.int32, device=dev)
+            sub_label = None if pose_label is None else pose_label[uniq].contiguous()
+            if int(uniq.shape[0]):
+                self.evaluate(poses[uniq].contiguous(), pose_model[uniq].contiguous(), sub_label, None,
+                              calc_obs_cost=False, dbg_zs=zs, stream=stream, **kw)
+            pose_label = sub_label
+        n = int(zs.shape[0])
+        # the kernel trusts the sizes: a wrong stride or shape would be an out-of-bounds read on the device
+        if S < 0:
+            raise ValueError("evaluate_states: state_off needs at least one entry")
+        if stride > 0 and self.width % stride == 0:  # otherwise the call itself refuses
+            nsamp = (self.width // stride) * ((self.height + stride - 1) // stride)
+            if zs.numel() != n * nsamp:
+                raise ValueError(f"evaluate_states: zs holds {zs.numel()} values, not {n} x {nsamp} samples of stride {stride}")
+        if pose_label is not None and pose_label.numel() != n:
+            raise ValueError(f"evaluate_states: pose_label has {pose_label.numel()} entries for {n} z-buffers")
+        if state_obs_total is not None and state_obs_total.numel() != S:
+            raise ValueError(f"evaluate_states: state_obs_total has {state_obs_total.numel()} entries for {S} states")
+        rc, oc, df = (torch.empty(S, dtype=torch.float32, device=dev) for _ in range(3))
+        vis = torch.empty(nnz, dtype=torch.int32, device=dev) if member_counts else None
+        bad = torch.empty(nnz, dtype=torch.int32, device=dev) if member_counts else None
+        p = EvalParams(int(cost_type), int(bool(calc_obs_cost)), int(stride), float(depth_factor),
+                       float(sensor_resolution), float(occlusion_threshold), 0.0)
+        self._check(self.lib.pcore_evaluate_states(
+            self._h, _ptr(zs, torch.int32, "zs") if n else None, n, _ptr(pose_label, torch.int32, "pose_label"),
+            _ptr(off, torch.int32, "state_off"), _ptr(member, torch.int32, "state_member") if nnz else None, S,
+            _ptr(state_obs_total, torch.float32, "state_obs_total"), ctypes.byref(p), _ptr(rc, torch.float32, "rc"),
+            _ptr(oc, torch.float32, "oc"), _ptr(df, torch.float32, "diff"),
+            _ptr(vis, torch.int32, "vis") if nnz else None, _ptr(bad, torch.int32, "bad") if nnz else None, nnz,
+            _stream(stream)))
+        return rc, oc, df, vis, bad
+
     def capture_evaluate(self, poses: torch.Tensor, pose_model: torch.Tensor, pose_label: Optional[torch.Tensor],
                          pose_obs_total: Optional[torch.Tensor], **kw):
         """Stage COST of a fixed-size batch as a HIP graph (torch.cuda.CUDAGraph over the C-ABI launches).

@@ -146,6 +146,7 @@ struct pcore_ctx {
     pcore_camera p2p_cam{};
     DevBuf<float4> p2p_pcd, p2p_normal;
     DevBuf<int64_t> topk_part;  // pcore_select_topk: one partial list per (slice, model)
+    DevBuf<uint32_t> state_bitmap;  // pcore_evaluate_states: explained bitmaps of clouds above PCORE_STATE_LDS_OBS
 };
 
 namespace pcore {

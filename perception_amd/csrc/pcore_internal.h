@@ -344,5 +344,33 @@ hipError_t launch_sample_source(const int32_t* src_depth, const uint8_t* src_mas
                                 int stride, int32_t* src_s, uint8_t* lab_s, hipStream_t s);
 hipError_t launch_select(const float* rc, const float* oc, const int32_t* pose_model, int num_poses,
                          int64_t index_base, int num_models, int64_t* keys, hipStream_t s);
+// pcore_state_cost.hip: stage COST of composed states (pcore_evaluate_states; DESIGN.md section 2, "State cost")
+struct StateCostArgs {
+    const int32_t* zs;            // num_poses x hs x ws sampled z-buffers after source occlusion
+    int32_t num_poses;
+    const int32_t* pose_label;    // nullptr: 3-DoF (the whole cloud's grid, grids[num_grids])
+    const int32_t* state_off;     // num_states + 1
+    const int32_t* state_member;  // num_members
+    int32_t num_states, num_members;
+    const float* state_obs_total;
+    int32_t stride, ws, hs;
+    float cx, cy, fx, fy, depth_factor;
+    const LabelGrid* grids;
+    const int32_t* cell_start;
+    const float4* grid_pts;
+    const int32_t* seg_lo;        // num_grids + 1: first label-sorted position of every segment
+    int32_t num_grids;
+    int32_t bitmap_words;         // one bit per observed point
+    uint32_t* scratch_bitmap;     // state_cost_scratch_blocks() x bitmap_words; nullptr: the bitmap lives in LDS
+    float r2;
+    int32_t calc_obs;
+    float* out_rc;
+    float* out_oc;
+    float* out_diff;
+    int32_t* out_member_vis;      // nullable, num_members, zero before the launch
+    int32_t* out_member_bad;
+};
+int state_cost_scratch_blocks(int num_states, const DeviceInfo& d);
+hipError_t launch_state_cost(const StateCostArgs& a, const DeviceInfo& d, hipStream_t s);
 
 }  // namespace pcore

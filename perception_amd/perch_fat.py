@@ -55,6 +55,8 @@ PERCH_PARAM_DEFAULTS = {
     "use_model_specific_search_resolution": ("use_model_specific_search_resolution", False),
     # a build extension (no reference counterpart): the staged search's shortlist per model, 0 = refine every state
     "icp_top_k": ("icp_top_k", 0),
+    # a build extension: the joint search over the joint_top_k best candidates per model after the greedy search, 0 = off
+    "joint_top_k": ("joint_top_k", 0),
     # build extensions: the nearest-neighbour scene of icp_type 5 (its radius in metres, its window's half-width in pixels)
     "nn_max_dist_diff": ("nn_max_dist_diff", 0.01),
     "nn_window": ("nn_window", 32),

@@ -25,10 +25,11 @@ import numpy as np
 import torch
 
 from . import io as pio
-from ._native import (COST_DEPTH_6DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, NN_MAX_DIST_DIFF, NN_WINDOW,
+from ._native import (COST_DEPTH_6DOF, COST_RGBD_3DOF, ICP_K, ICP_MAX_ITER, ICP_ROT_EPS, ICP_TRANS_EPS, NN_MAX_DIST_DIFF, NN_WINDOW,
                       P2P_MAX_DIST_DIFF, P2P_MAX_ITER, P2P_REL_FITNESS, P2P_REL_RMSE, PCORE_KEY_NONE, PCORE_TOPK_MAX)
 from .core import PoseCore, decode_keys
 from .distributed import allgather_topk_keys, allreduce_min_keys, shard_range
+from .joint import joint_search, state_obs_total
 from .model import (Model, chain_matmul_batch, compute_proj, init_from_eigen_batch, matmul_lazy, pose_matrix_batch,
                     quat_from_matrix_eigen_batch, so3_log_batch)
 from .staged import refine_shortlist, select_refined, shortlist_members
@@ -82,6 +83,11 @@ class PerchParams:
     # every state without ICP, refine only the icp_top_k best per model (1 .. 64) and select among the refined;
     # 0 = the reference's flow, every state refined
     icp_top_k: int = 0
+    # the joint search (a build extension): after the search above, the joint_top_k best
+    # candidates per model by their final costs (with icp_top_k: of the refined rows) are searched jointly on the cost of
+    # the composed state (perception_amd/joint.py) and the winners replaced by its result; 0 = off.  Depth costs only,
+    # one rank only
+    joint_top_k: int = 0
 
 
 @dataclass
@@ -505,6 +511,78 @@ class ObjectRecognizer:
                              "the staged search needs icp_type 3, 4 or 5")
         return k if inp.use_icp and p.icp_type in (3, 4, 5) else 0
 
+    def _joint_top_k(self) -> int:
+        """The shortlist length of the joint search, 0 when it is off; raises before any GPU work where it cannot run."""
+        k = int(self.params.joint_top_k)
+        if k == 0:
+            return 0
+        if not 1 <= k <= PCORE_TOPK_MAX:
+            raise ValueError(f"joint_top_k must lie in [0, {PCORE_TOPK_MAX}], got {k}")
+        if self._cost_type() == COST_RGBD_3DOF:
+            raise ValueError("joint_top_k: the state cost has no colour gate (cost_type 1); use the depth cost")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and \
+                torch.distributed.get_world_size() > 1:
+            raise ValueError("joint_top_k: the joint search runs on one rank (the shortlist poses are not exchanged)")
+        return k
+
+    def _state_obs_counts(self):
+        """joint.state_obs_total's obs_counts: the observed points per label (6-DoF) or of the whole cloud (3-DoF)."""
+        if self._cost_type() == COST_DEPTH_6DOF:
+            return self.segmented_count
+        return float(len(self.obs_xyz_host))
+
+    def _joint_refine(self, k: int, K: int, lo: int, keys: torch.Tensor):
+        """The joint search over the k best candidates per model by the shard's final costs (of the refined rows when
+        the search ran staged): keys[m] becomes the key of the candidate the joint state holds for model m."""
+        p = self.params
+        adj, pm, pl, cost_type, rows = self._last_shard
+        rc, oc, _ = self._last_costs_dev
+        if rows is not None:  # the selection's own device: -1 (the invalid cost) outside the refined rows
+            sel_rc = torch.full_like(rc, -1.0)
+            sel_oc = torch.full_like(oc, -1.0)
+            sel_rc[rows], sel_oc[rows] = rc[rows], oc[rows]
+            rc, oc = sel_rc, sel_oc
+        topk = self.core.select_topk(rc, oc, pm, K, k, index_base=lo)
+        _, idx = decode_keys(topk)
+        shortlists = np.where(idx >= 0, idx - lo, -1)
+        res = joint_search(self.core, adj, pm, pl if cost_type == COST_DEPTH_6DOF else None, shortlists,
+                           self._state_obs_counts(), cost_type=cost_type, stride=p.gpu_stride,
+                           depth_factor=p.gpu_depth_factor, sensor_resolution=p.sensor_resolution,
+                           occlusion_threshold=p.gpu_occlusion_threshold)
+        for m in range(K):
+            if res.slot[m] >= 0:
+                keys[m] = topk[m, res.slot[m]]
+        self.last_joint = res
+        self.last_joint_shortlist = shortlists
+
+    def score_state(self, res):
+        """The greedy state's cost: the winners of the last compute_greedy_render_poses ((model, cost, index, ContPose)
+        tuples, or a LocalizationResult) scored as ONE state by PoseCore.evaluate_states on the search's own adjusted
+        poses -- the numeric companion of render_state.  -> dict(rc, oc, diff: the state's costs; total: the observed
+        points it has to explain; vis, bad: every winner's points and bad points in the state, in the order of `res`)."""
+        if isinstance(res, LocalizationResult):
+            res = [(self.model_names.index(n), c, i, q) for n, c, i, q in
+                   zip(res.model_names, res.costs, res.indices, res.detected_poses)]
+        if getattr(self, "_last_shard", None) is None:
+            raise ValueError("score_state: no search has run on this recognizer")
+        p = self.params
+        adj, pm, pl, cost_type, _ = self._last_shard
+        lo = self._last_lo
+        members = [int(r[2]) - lo for r in res]
+        if any(not 0 <= m < int(adj.shape[0]) for m in members):
+            raise ValueError("score_state: a winner lies outside this rank's shard")
+        six = cost_type == COST_DEPTH_6DOF
+        if cost_type == COST_RGBD_3DOF:
+            raise ValueError("score_state: the state cost has no colour gate (cost_type 1)")
+        label_h = pl.cpu().numpy() if six else None
+        tot = state_obs_total(members, label_h, self._state_obs_counts())
+        rc, oc, df, vis, bad = self.core.evaluate_states(
+            [members], pl if six else None, torch.tensor([float(tot)], dtype=torch.float32, device=self.device),
+            poses=adj, pose_model=pm, cost_type=cost_type, stride=p.gpu_stride, depth_factor=p.gpu_depth_factor,
+            sensor_resolution=p.sensor_resolution, occlusion_threshold=p.gpu_occlusion_threshold)
+        return {"rc": float(rc[0]), "oc": float(oc[0]), "diff": float(df[0]), "total": float(tot),
+                "vis": vis.cpu().numpy(), "bad": bad.cpu().numpy()}
+
     def _p2p_kw(self) -> dict:
         """evaluate_p2p's ICP arguments for icp_type 4 (the projective scene) or 5 (the nearest-neighbour one)."""
         p = self.params
@@ -543,6 +621,7 @@ class ObjectRecognizer:
         select_refined(self.core, refined, pm, K, lo, keys)
         sub, a, it, r, o, d = refined
         rc[sub], oc[sub], df[sub], adj_all[sub], iters[sub] = r, o, d, a, it
+        self._refined_rows = sub
         torch.cuda.synchronize(self.device)
         return self.core.stats(reset=True) if p.icp_type == 3 else None
 
@@ -551,7 +630,9 @@ class ObjectRecognizer:
         t0 = time.perf_counter()
         p = self.params
         staged = self._staged_top_k(inp)
+        joint = self._joint_top_k()
         self._check_state_hooks()
+        self._last_shard = None
         if self._device_state_path:
             dstates = self._successor_states_device(inp)
             n_total = 0 if dstates is None else int(dstates[0].shape[0])
@@ -633,6 +714,7 @@ class ObjectRecognizer:
                 icp_time = float(st["icp_runtime"])
                 peak_mb = st["peak_memory_usage"]  # gpu_stats.peak_memory_usage (MB)
             self._last_costs_dev = (rc, oc, df)  # read back only on request (_last_costs)
+        self._refined_rows = None
         if staged:  # every rank takes part in the shortlist exchange, with or without a shard
             ti = time.perf_counter()
             shard = (poses, pm, pl, tot, cost_type, rc, oc, df, adj_all, iters) if n > 0 else None
@@ -641,6 +723,14 @@ class ObjectRecognizer:
             if st is not None:
                 icp_time = float(st["icp_runtime"])
                 peak_mb = st["peak_memory_usage"]
+        if n > 0:  # handles, not copies: score_state and the joint search read the shard's own tensors
+            self._last_shard = (adj_all, pm, pl, cost_type, self._refined_rows if staged else None)
+            self._last_lo = lo
+            if joint:
+                ti = time.perf_counter()
+                self._joint_refine(joint, K, lo, keys)
+                torch.cuda.synchronize(self.device)
+                gpu_s += time.perf_counter() - ti
         allreduce_min_keys(keys)
         cost, idx = decode_keys(keys)
         # winning adjusted poses: the owning rank contributes, the others add zeros
@@ -783,6 +873,7 @@ class ObjectRecognizer:
 
     # -- ObjectRecognizer::LocalizeObjectsGreedyRender (object_recognizer.cpp:290-342) -------------
     def localize_objects_greedy_render(self, inp: RecognitionInput) -> LocalizationResult:
+        self._joint_top_k()  # refuses before any GPU work
         if not self.models or self.model_names != list(inp.model_names):
             self.set_static_input(inp.model_names, six_dof=inp.use_external_pose_list == 1)
         t0 = time.perf_counter()

@@ -305,6 +305,9 @@ class TabletopRecognizer(ObjectRecognizer):
         """LocalizeObjectsGreedyRender in 3-DoF mode: (model, cost, index, ContPose x y z qx qy qz qw).  use_icp = 1
         (with params.icp_type 0) refines every grid state by planar ICP before it is scored, and the ContPose is the
         adjusted state's."""
+        # the joint search refuses before any GPU work (set_input_3dof decides use_colour from the same two facts)
+        if int(self.params.joint_top_k) and self.params.use_color_cost and rgb is not None:
+            raise ValueError("joint_top_k: the state cost has no colour gate (cost_type 1); use the depth cost")
         if not self.models or self.model_names != list(model_names):
             self.set_static_input(model_names, six_dof=False)
         self.set_input_3dof(depth, camera_pose, depth_factor, rgb)

@@ -504,6 +504,62 @@ def run_c3_topk(per_model=10000, runs=5, ks=(1, 4, 16, 64)):
     print(json.dumps(out), flush=True)
 
 
+def run_c3_joint(per_model=10000, runs=5, k=16):
+    """c3_joint: one sweep of the joint search (perception_amd/joint.py) on C3's batch (5 objects, 50k 6-DoF poses) at
+    K = `k`: the evaluate(dbg_zs) call over the shortlisted candidates that feeds the sweep, the evaluate_states call
+    over the sweep's S states of M members, and for scale a plain evaluate over the same S x M member poses -- `runs`
+    alternating runs each after one warm-up, medians and every run."""
+    from perception_amd.joint import state_obs_total, sweep_states
+    w = workloads.build(names=C3_NAMES, poses_per_model=per_model, cam=syn.CAM_640)
+    n = int(w.poses.shape[0])
+    dev = w.poses.device
+    rc, oc, _ = w.core.evaluate(w.poses, w.pose_model, w.pose_label, w.pose_obs_total, stride=w.stride)
+    _, idx = decode_keys(w.core.select_topk(rc, oc, w.pose_model, w.num_models, k))
+    shortlists = np.where(idx >= 0, idx, -1)
+    used = np.unique(shortlists[shortlists >= 0])
+    compact = {int(c): i for i, c in enumerate(used)}
+    sub = torch.from_numpy(used).to(dev)
+    poses, pm, pl = w.poses[sub].contiguous(), w.pose_model[sub].contiguous(), w.pose_label[sub].contiguous()
+    nsamp = (w.core.width // w.stride) * ((w.core.height + w.stride - 1) // w.stride)
+    zs = torch.zeros((len(used), nsamp), dtype=torch.int32, device=dev)
+    slot = [0 if shortlists[m][0] >= 0 else -1 for m in range(w.num_models)]
+    states, _ = sweep_states(shortlists, slot)
+    label_h = w.pose_label.cpu().numpy()
+    obs_lab = w.obs_label.cpu().numpy()
+    counts = np.bincount(obs_lab[obs_lab >= 0], minlength=w.num_models)
+    tot = torch.from_numpy(np.array([state_obs_total(st, label_h, counts) for st in states], np.float32)).to(dev)
+    members = [[compact[c] for c in st] for st in states]
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int32)).to(dev)
+    mem = torch.from_numpy(np.concatenate(members).astype(np.int32)).to(dev)
+    flat = sub[mem.long()]
+    fp, fm, fl, ft = (t[flat].contiguous() for t in (w.poses, w.pose_model, w.pose_label, w.pose_obs_total))
+    res = {}
+
+    def feed():
+        res["feed"] = w.core.evaluate(poses, pm, pl, None, calc_obs_cost=False, stride=w.stride, dbg_zs=zs)
+
+    def states_call():
+        res["states"] = w.core.evaluate_states((off, mem), pl, tot, zs=zs, stride=w.stride)
+
+    def plain():
+        res["plain"] = w.core.evaluate(fp, fm, fl, ft, stride=w.stride)
+
+    fns = {"feed": feed, "states": states_call, "plain": plain}
+    for fn in fns.values():
+        _once(fn)
+    t = {name: [] for name in fns}
+    for _ in range(runs):  # alternating
+        for name, fn in fns.items():
+            t[name].append(_once(fn))
+    med = {name: float(np.median(v)) for name, v in t.items()}
+    print(json.dumps({"config": "c3_joint", "poses": n, "models": w.num_models, "stride": w.stride, "runs": runs, "k": k,
+                      "shortlisted": int(len(used)), "states": len(states), "members_per_state": len(states[0]),
+                      "member_poses": int(mem.shape[0]), "evaluate_dbg_zs_s": med["feed"],
+                      "evaluate_states_s": med["states"], "evaluate_member_poses_s": med["plain"],
+                      "evaluate_dbg_zs_s_all": t["feed"], "evaluate_states_s_all": t["states"],
+                      "evaluate_member_poses_s_all": t["plain"]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="C1,C2,C3,C4,C5")
@@ -527,6 +583,8 @@ def main():
         run_c3_nn(per_model=max(1, int(10000 * sc)))
     if "c3_topk" in sel:
         run_c3_topk(per_model=max(1, int(10000 * sc)))
+    if "c3_joint" in sel:
+        run_c3_joint(per_model=max(1, int(10000 * sc)))
     if "C2" in sel:
         run("C2", ["003_cracker_box"], int(10000 * sc), syn.CAM_640, False, a.steps, a.warmup)
     if "C3" in sel:

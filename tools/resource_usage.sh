@@ -10,7 +10,7 @@ for SRC in $(python -c "from perception_amd import build; print(' '.join(build.S
     -Rpass-analysis=kernel-resource-usage 2>&1 | python -c "
 import re, sys
 cur = None
-KERNELS = ('gicp_kernel', 'fused_cost', 'render_cloud_kernel', 'window_probe_kernel', 'covariance_kernel', 'planar_icp', 'p2p_icp', 'scene_kernel', 'scene_finalize', 'topk_')
+KERNELS = ('gicp_kernel', 'fused_cost', 'render_cloud_kernel', 'window_probe_kernel', 'covariance_kernel', 'planar_icp', 'p2p_icp', 'scene_kernel', 'scene_finalize', 'topk_', 'state_cost')
 for l in sys.stdin:
     m = re.search(r'remark: Function Name: (\S+)', l)
     if m:
