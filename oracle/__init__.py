@@ -6,8 +6,10 @@ product package (perception_amd) never imports, links or calls it.
 This is a literal restatement of the reference's CUDA/host code (file:line citations in
 pcore_oracle.cpp).  The whole reference path cannot be built here, but its stage kernels can, for the host
 (oracle/ref_host/, build_ref()): tests/golden/refk_*.npz are their outputs, and tests/test_reference_goldens.py holds
-the raster, cloud and cost restatements to them bit for bit ("Oracle").  The pin is to the reference's source
-under this oracle's float flags, not to an nvcc binary.
+the raster, cloud and cost restatements to them bit for bit ("Oracle").  So can cuda_icp's host sources:
+tests/golden/refk_icp_*.npz and tests/test_reference_icp_goldens.py do the same for ref_cpu_path.cpp's scene, rows and
+ICP loop, all but the 6 x 6 solve.  The pin is to the reference's source under this oracle's float flags, not to an
+nvcc binary.
 """
 from __future__ import annotations
 
@@ -35,9 +37,11 @@ def build() -> str:
 
 
 def build_ref(reference_root=None) -> str:
-    """Compile the reference's own stage kernels for the host (oracle/ref_host/): oracle/_ref/ref_host, and
-    oracle/_ref/ref_host_san with -fsanitize=address,undefined, both stand-alone programs that are never loaded into
-    Python.  The reference root is PCORE_REFERENCE_ROOT (default /root/reference).  Not part of
+    """Compile the reference's own sources for the host (oracle/ref_host/): the stage kernels as oracle/_ref/ref_host
+    and the cuda_icp point-to-plane ICP as oracle/_ref/ref_icp, each also as <name>_san with
+    -fsanitize=address,undefined -- stand-alone programs that are never loaded into Python.  ref_icp is built without
+    OpenMP (its sums then run in index order) and links ref_cpu_path.cpp for the 6 x 6 solve, the one part that is
+    not the reference's.  The reference root is PCORE_REFERENCE_ROOT (default /root/reference).  Not part of
     __graft_entry__.build(): the reference exists only where the goldens are made.  Returns oracle/_ref."""
     from . import ref_host
     from .ref_host import filter_sources
@@ -50,13 +54,21 @@ def build_ref(reference_root=None) -> str:
     # -fpermissive and clang only warns about.  The float flags are the oracle's.
     cxx = os.environ.get("PCORE_REF_CXX") or shutil.which("clang++") or os.path.join(
         os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++")
-    base = [cxx, "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-            "-fno-unsafe-math-optimizations", "-mno-fma", "-w", "-include",
-            os.path.join(rh, "shim", "ref_shim.h"), "-I", os.path.join(rh, "shim"), "-I", src,
-            os.path.join(rh, "driver.cpp")]
-    subprocess.run(base + ["-O2", "-o", os.path.join(out, "ref_host")], check=True)
-    subprocess.run(base + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-o", os.path.join(out, "ref_host_san")], check=True)
+    flags = [cxx, "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
+             "-fno-unsafe-math-optimizations", "-mno-fma", "-w", "-include",
+             os.path.join(rh, "shim", "ref_shim.h"), "-I", os.path.join(rh, "shim"), "-I", rh]
+    icp = os.path.join(src, "cuda_icp")
+    programs = {
+        "ref_host": ["-I", src, os.path.join(rh, "driver.cpp")],
+        "ref_icp": ["-I", os.path.join(icp, "include"), "-I", _HERE, os.path.join(rh, "driver_icp.cpp"),
+                    os.path.join(icp, "icp.cpp"), os.path.join(icp, "scene", "common.cpp"),
+                    os.path.join(icp, "scene", "depth_scene", "depth_scene.cpp"),
+                    os.path.join(icp, "scene", "pcd_scene", "pcd_scene.cpp"), os.path.join(_HERE, "ref_cpu_path.cpp")],
+    }
+    for name, files in programs.items():
+        subprocess.run(flags + files + ["-O2", "-o", os.path.join(out, name)], check=True)
+        subprocess.run(flags + files + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                                        "-fno-sanitize-recover=all", "-o", os.path.join(out, name + "_san")], check=True)
     return out
 
 

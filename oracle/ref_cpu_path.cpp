@@ -23,9 +23,15 @@
 // Deterministic choices (the reference leaves them open): the OpenMP `reduction(+: reducer)` over points
 // (icp.cpp:128-133) has no fixed order; here every pose runs on one thread and its points are summed in
 // index order.  Poses run in parallel instead (the reference runs render_cpu over poses and ICP over
-// points).  Eigen is not vendored (no headers in this image): LDLT and the AngleAxis products follow
-// Eigen 3.3's published unblocked algorithms; parity of this row is therefore unpinned against the
-// reference binary, like every other row.
+// points).
+//
+// Parity.  Pinned bit for bit to the reference's own sources compiled for the host (oracle/ref_host/driver_icp.cpp,
+// tests/golden/refk_icp_*.npz, tests/test_reference_icp_goldens.py): depth2cloud, dep2pcd / pcd2dep, the scene and
+// its normals, the 29-float row, and the whole loop of icp_point2plane -- acceptance tests, both exits, the extra
+// turn, transform_pcd, the order of the Mat4x4f product -- with the sums in index order.  NOT pinned: ldlt_solve6 and
+// vec6_to_mat4.  Eigen is not vendored (no headers in this image), so they follow Eigen 3.3's published unblocked
+// algorithms, and the reference program that makes those fixtures calls orc_ref_solver666 below for its solve: a
+// misreading of Eigen there would pass.  render_cpu is not pinned either.
 #include "pcore_oracle.h"
 
 #include <climits>

@@ -1,7 +1,8 @@
-"""The reference's own stage kernels, compiled for the host -- TEST INFRASTRUCTURE ONLY (README.md in this folder).
+"""The reference's own stage kernels and ICP sources, compiled for the host -- TEST INFRASTRUCTURE ONLY (README.md in
+this folder).
 
-oracle.build_ref() builds oracle/_ref/ref_host and oracle/_ref/ref_host_san from the reference root; this module writes
-a request, runs one of the two programs on it and reads the result.  The programs are stand-alone: nothing of them is
+oracle.build_ref() builds oracle/_ref/ref_host, ref_icp and their _san twins from the reference root; this module writes
+a request, runs one of the programs on it and reads the result.  The programs are stand-alone: nothing of them is
 loaded into Python.  They exist only where the reference root does (the golden generator and the freshness test)."""
 from __future__ import annotations
 
@@ -15,7 +16,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REF_DIR = os.path.join(os.path.dirname(_HERE), "_ref")
 DEFAULT_ROOT = "/root/reference"
 
-OP_RENDER, OP_CLOUD, OP_COSTS, OP_COLOUR = 1, 2, 3, 4
+OP_RENDER, OP_CLOUD, OP_COSTS, OP_COLOUR = 1, 2, 3, 4                    # ref_host (driver.cpp)
+OP_ICP_SCENE, OP_ICP_ROWS, OP_ICP_RUN, OP_ICP_DEPTH2CLOUD = 11, 12, 13, 14  # ref_icp (driver_icp.cpp)
 _DTYPES = [np.dtype(np.uint8), np.dtype(np.int32), np.dtype(np.float32), np.dtype(np.float64)]
 
 
@@ -79,11 +81,12 @@ def read_bundle(path) -> dict:
     return out
 
 
-def run(request: dict, sanitized: bool = True) -> dict:
-    """One request through ref_host_san (or ref_host): the result arrays.  Anything on the program's stderr, or a
+def run(request: dict, sanitized: bool = True, program: str = "ref_host") -> dict:
+    """One request through <program>_san (or <program>): the result arrays.  Anything on the program's stderr, or a
     non-zero exit, is an error: with the sanitized build that is how an out-of-bounds access or undefined behaviour in
-    the reference's code shows."""
-    exe = os.path.join(REF_DIR, "ref_host_san" if sanitized else "ref_host")
+    the reference's code shows.  What it prints to stdout is dropped (get_normal and init_Scene_nn_cpu announce
+    themselves there)."""
+    exe = os.path.join(REF_DIR, program + ("_san" if sanitized else ""))
     if not os.path.exists(exe):
         raise FileNotFoundError(f"{exe}: run oracle.build_ref() first")
     env = dict(os.environ)

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
+#include <numeric>  // pcd_scene.cpp names std::iota and gets it through OpenCV's headers
 #include <string>
 #include <vector>
 
@@ -77,14 +78,54 @@ template <typename T, int R, int C>
 inline std::ostream& operator<<(std::ostream& os, const Matrix<T, R, C>&) { return os; }
 }  // namespace Eigen
 
-// ---- OpenCV / assimp: model.h names them in members the stages never call -----------------------------------
+// ---- OpenCV: a dense single-channel matrix, as much of cv::Mat as model.h and cuda_icp's scenes name ---------
+// Rows are contiguous.  A copy copies the elements (OpenCV shares them; the sources here only read a copy).
+// convertTo is this file's own code: CV_32S -> CV_16U by OpenCV's documented rule, saturate_cast<ushort>(int)
+// (values below 0 become 0, values above 65535 become 65535).  It is pinned to that rule, not to an OpenCV build.
+#define CV_16U 2
+#define CV_32S 4
 #define CV_32F 5
+typedef unsigned short ushort;
 namespace cv {
+template <typename T> inline T saturate_cast(int v);
+template <> inline ushort saturate_cast<ushort>(int v) { return (ushort)((unsigned)v <= 65535u ? v : v > 0 ? 65535 : 0); }
 struct Mat {
-    int type() const { return CV_32F; }
-    template <typename T> T at(int, int) const { return T(); }
+    int rows = 0, cols = 0;
+    Mat() {}
+    Mat(int rows_, int cols_, int type) : rows(rows_), cols(cols_), type_(type), data_((size_t)rows_ * cols_ * elem(type)) {}
+    int type() const { return type_; }
+    template <typename T> T& at(int r, int c) { return *reinterpret_cast<T*>(data_.data() + offset<T>(r, c)); }
+    template <typename T> const T& at(int r, int c) const { return *reinterpret_cast<const T*>(data_.data() + offset<T>(r, c)); }
+    template <typename T> T* ptr() { return reinterpret_cast<T*>(data_.data()); }
+    template <typename T> const T* ptr() const { return reinterpret_cast<const T*>(data_.data()); }
+    void convertTo(Mat& dst, int rtype) const {
+        if (type_ != CV_32S || rtype != CV_16U) { std::fprintf(stderr, "cv::Mat::convertTo: only CV_32S -> CV_16U\n"); std::abort(); }
+        Mat out(rows, cols, CV_16U);
+        for (int r = 0; r < rows; r++)
+            for (int c = 0; c < cols; c++) out.at<ushort>(r, c) = saturate_cast<ushort>(at<int32_t>(r, c));
+        dst = out;
+    }
+
+private:
+    static size_t elem(int type) {
+        if (type == CV_16U) return 2;
+        if (type == CV_32S || type == CV_32F) return 4;
+        std::fprintf(stderr, "cv::Mat: type %d is not in the shim\n", type);
+        std::abort();
+    }
+    template <typename T> size_t offset(int r, int c) const {
+        if (sizeof(T) != elem(type_) || r < 0 || r >= rows || c < 0 || c >= cols) {
+            std::fprintf(stderr, "cv::Mat::at(%d, %d) outside %d x %d, or an element of the wrong size\n", r, c, rows, cols);
+            std::abort();
+        }
+        return ((size_t)r * cols + c) * sizeof(T);
+    }
+    int type_ = CV_32F;
+    std::vector<uint8_t> data_;
 };
 }  // namespace cv
+
+// ---- assimp: model.h names these in members the stages never call --------------------------------------------
 struct aiVector3D { float x = 0, y = 0, z = 0; };
 struct aiMatrix4x4 { float m[16] = {}; };
 struct aiScene;
