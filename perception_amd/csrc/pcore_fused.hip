@@ -16,6 +16,7 @@
 #include "pcore_fused_probe.h"
 
 #include <algorithm>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -93,8 +94,10 @@ struct SampleWin {
     // finite and the camera rows' bounds over the model's box far from FLT_MAX
     int sparse;
     // a fastdiv pose whose proven box of computed screen coordinates (pose_window) lies inside the image, [0, W-1] x
-    // [0, H-1]: the vertex pass needs no clamp to the image (vertex_bounds) and the fragment test's area reciprocal
-    // no scaling steps (pcore_fdiv.h, recip_interior).  A property of the pose: a chunk keeps its window's flag.
+    // [0, H-1], and whose window none of pose_window's clamps to the sampled image has cut: the vertex pass needs no
+    // clamp to the image (vertex_bounds), the fragment test's area reciprocal no scaling steps (pcore_fdiv.h,
+    // recip_interior) and the triangle stage no clip to the whole window (raster_phase, WHOLE).  A property of the pose:
+    // a chunk keeps its window's flag.
     int interior;
 };
 
@@ -114,7 +117,9 @@ __device__ __forceinline__ void raster_sample(const TriRec& r, int kx, int ky, i
         in = fragment_rz<BARY>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d, exact_z);
     else
         in = fragment<BARY>(r.a0, r.a1, r.b0, r.b1, r.c0, r.c1, r.z0, r.z1, r.z2, P0, P1, d, w.fastdiv != 0);
-    const int k = (int)__umul24((uint32_t)(ky - w.y0), (uint32_t)w.nx) + (kx - w.x0);  // inside the window
+    // inside the window: (ky - y0) nx + (kx - x0), as one multiply-add of the sample's halves less the wave-uniform
+    // y0 nx + x0 (ky and nx are below 2^24 and their product below 2^32, as in the product of (ky - y0) it replaces)
+    const int k = (int)(__umul24((uint32_t)ky, (uint32_t)w.nx) + (uint32_t)kx) - (w.y0 * w.nx + w.x0);
     if constexpr (IDPASS) {
         if (in && d == zbuf[k]) atomicMin(&cid[k], (int32_t)id);
     } else {
@@ -211,6 +216,28 @@ __device__ __forceinline__ uint2 vertex_bounds(float sx, float sy, int s, float 
         lo1 = cvt_rpi(sy);
         hi0 = cvt_flr(sx);
         hi1 = cvt_flr(sy);
+        if constexpr (STRIDE == 8) {
+            // The two words built in place and shifted as int16 pairs:
+            //   (A0, B0) = (lo0 + 7, H + 6 - hi1) >> 3      (A1, B1) = (hi0, H - 1 - lo1) >> 3
+            // The four converted values lie in [0, 16383] (sx in [0, W-1], sy in [0, H-1], W, H <= 16384), so every
+            // half lies in [0, H + 6], inside int16: each is the 32-bit expression of the scalar form bit for bit (H - 1
+            // - hi1 + 7 = H + 6 - hi1; a shift of a non-negative value).  The subtractions write the upper half of the
+            // word that already holds the lower one (SDWA, the rest of the destination preserved), and one packed shift
+            // per word divides both halves: five instructions for the nine of the scalar form (packing with
+            // v_cvt_pk_i16_i32 and a packed multiply-add by (1, -1) took eight: gfx9 reads one scalar constant per
+            // instruction).  A VALU write through dst_sel or of a packed result needs one wait state before a VALU
+            // instruction reads the register (the compiler does not see into the asm): the order below and the closing
+            // s_nop give it to both words.
+            uint32_t p0 = (uint32_t)(lo0 + 7), p1 = (uint32_t)hi0;
+            asm("v_sub_u32_sdwa %0, %2, %3 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
+                "v_sub_u32_sdwa %1, %4, %5 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD\n\t"
+                "v_pk_ashrrev_i16 %0, 3, %0 op_sel_hi:[0,1]\n\t"
+                "v_pk_ashrrev_i16 %1, 3, %1 op_sel_hi:[0,1]\n\t"
+                "s_nop 0"  // the same wait state after the last packed write, whatever the compiler puts next
+                : "+v"(p0), "+v"(p1)
+                : "s"(H + 6), "v"(hi1), "s"(H - 1), "v"(lo1));
+            return make_uint2(p0, p1);
+        }
     } else {
         lo0 = cvt_rpi(__builtin_amdgcn_fmed3f(sx, 0.0f, 65536.0f));
         lo1 = cvt_rpi(__builtin_amdgcn_fmed3f(sy, 0.0f, 65536.0f));
@@ -233,11 +260,24 @@ __device__ __forceinline__ uint2 vertex_bounds(float sx, float sy, int s, float 
 // instantiates the three and picks one per pose, so a fastdiv pose's steps carry no NaN-triangle test or range checks at
 // all, and an interior pose's no clamp of its vertices to the image and no scaling steps in the area's reciprocal), or
 // -1 to read the fastdiv flag from the window (the colour id pass: the general fragment test and clamps)
-template <int STRIDE, bool IDPASS = false, int FD = -1>
+//
+// WHOLE: sw_in is the pose's own window, not a chunk of it (the un-chunked copy of fused_pose / render_cloud_kernel).
+// With FD = 2 the triangle stage then does not clip the triangle's window to sw.  pose_window proves a box [xlo, xhi] x
+// [ylo, yhi] that holds every vertex's computed sx, sy, and an interior pose's window is, unclamped (pose_window grants
+// the class only then), [X0, X1] x [Y0, Y1] = [floor((xlo-1)/s), floor(xhi/s)] x [floor((H-1-yhi)/s), floor((H-ylo)/s)].
+// The bounds of a vertex (vertex_bounds) are A0 = ceil(rpi(sx)/s) >= (sx - 0.5)/s > (xlo - 1)/s, A1 = floor(floor(sx)/s)
+// <= sx/s <= xhi/s, B0 = ceil((H-1-floor(sy))/s) >= (H-1-yhi)/s and B1 = floor((H-1-rpi(sy))/s) <= (H-0.5-sy)/s <
+// (H-ylo)/s: integers, so X0 <= A0, A1 <= X1, Y0 <= B0, B1 <= Y1 for every vertex (the float quotients of pose_window
+// round monotonically and an integer is its own rounding, so the computed floors keep the inequalities).  A triangle's lo
+// is a minimum of (A0, B0) and its hi a maximum of (A1, B1) over three vertices, so max(lo, first) = lo and min(hi, last)
+// = hi in both halves whether the window is empty or not: the clip changes no bit of lo, hi or d.  A chunk is a proper
+// part of the window and keeps the clip.
+template <int STRIDE, bool IDPASS = false, int FD = -1, bool WHOLE = false>
 __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem& sm, int pose, const SampleWin& sw_in,
                                              int32_t* cid, FProf& fp) {
     SampleWin sw = sw_in;
     if constexpr (FD >= 0) sw.fastdiv = FD >= 1;
+    constexpr bool kNoClip = WHOLE && FD == 2 && !IDPASS;
     // the fragment test without its halves: the depth pass of a fastdiv pose only; with the unscaled area reciprocal:
     // of an interior pose only (pcore_fdiv.h)
     constexpr int kBary = IDPASS || FD < 1 ? 0 : FD;
@@ -277,7 +317,14 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
     // the pose window as int16 pairs (first sample, last sample); an empty window has last < first
     const short2v wfirst = {(short)sw.x0, (short)sw.y0};
     const short2v wlast = {(short)(sw.x0 + sw.nx - 1), (short)(sw.y0 + sw.ny - 1)};
-    uint2* ring = sm.ring + wave * kRecStride;
+    // The ring as 32-bit words behind one opaque LDS byte address in an SGPR: the compiler otherwise keeps the
+    // workgroup's LDS base and adds the ring's constant offset to every record address in a VALU instruction.
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    uint32_t ring_addr = (uint32_t)(uintptr_t)(lds_u32*)reinterpret_cast<uint32_t*>(sm.ring + wave * kRecStride);
+    asm("" : "+s"(ring_addr));
+    lds_u32* const ring = (lds_u32*)(uintptr_t)ring_addr;
+    auto ring_put = [ring](int slot, uint32_t x, uint32_t y) { ring[2 * slot] = x; ring[2 * slot + 1] = y; };
+    auto ring_get = [ring](int slot) { return make_uint2(ring[2 * slot], ring[2 * slot + 1]); };
     uint32_t* ring_id = IDPASS ? sm.ring_id + wave * kRecStride : nullptr;
     // record ring: wave-uniform monotone counters of appended and flushed records; record i lives in slot
     // i mod kRecCap.  Full 64-record batches are flushed as soon as they exist; a partial batch only when a
@@ -310,7 +357,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                 fs.batch(lane, min(count - base, kWave));
                 if (base + lane < count) {
                     const int j = (rec_done + base + lane) & (kRecCap - 1);
-                    const uint2 rec = ring[j];
+                    const uint2 rec = ring_get(j);
                     const uint32_t id = IDPASS ? ring_id[j] : 0u;
                     const int i0 = rec.x & 511, i1 = (rec.x >> 9) & 511, i2 = (rec.x >> 18) & 511;
                     const float2 q0 = vxy[i0], q1 = vxy[i1], q2 = vxy[i2];
@@ -464,8 +511,10 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                     short2v hi = __builtin_elementwise_max(__builtin_elementwise_max(as_s2(w0.y), as_s2(w1.y)), as_s2(w2.y));
                     // (fastdiv poses have finite screen coordinates: no NaN vertex)
                     if (!sw.fastdiv) nan_tri = lo.x < 0 && !pad;
-                    lo = __builtin_elementwise_max(lo, wfirst);
-                    hi = __builtin_elementwise_min(hi, wlast);
+                    if constexpr (!kNoClip) {  // (the whole window of an interior pose holds lo and hi: WHOLE above)
+                        lo = __builtin_elementwise_max(lo, wfirst);
+                        hi = __builtin_elementwise_min(hi, wlast);
+                    }
                     const short2v d = hi - lo;  // (nx - 1, ny - 1), negative where the window is empty
                     pos = __builtin_bit_cast(uint32_t, lo);
                     dbits = __builtin_bit_cast(uint32_t, d);
@@ -570,7 +619,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                 // one ballot round each; full 64-record batches are flushed after every round (<= 127 pending)
                 if (qd) {  // the record keeps the whole triangle slot word (the flush reads its 27 slot bits)
                     const int slot = (rec_total + mbcnt64(bq)) & (kRecCap - 1);
-                    ring[slot] = make_uint2(ct, pos);
+                    ring_put(slot, ct, pos);
                     if (IDPASS) ring_id[slot] = cidt;
                 }
                 rec_total += __popcll(bq);
@@ -584,7 +633,7 @@ __device__ __forceinline__ void raster_phase(const FusedArgs& a, const FusedSmem
                             const int nx = (int)(nxy & 0xffffu);
                             const int iy = nx == 1 ? q : (nx == 2 ? q >> 1 : 0), ix = q - iy * nx;
                             const int slot = (rec_total + mbcnt64(br)) & (kRecCap - 1);
-                            ring[slot] = make_uint2(ct, pos + (uint32_t)ix + ((uint32_t)iy << 16));
+                            ring_put(slot, ct, pos + (uint32_t)ix + ((uint32_t)iy << 16));
                             if (IDPASS) ring_id[slot] = cidt;
                         }
                         rec_total += __popcll(br);
@@ -656,15 +705,22 @@ __device__ __forceinline__ SampleWin pose_window(const FusedArgs& a, int model, 
     const float xlo = sx0 - mgx, xhi = sx1 + mgx, ylo = sy0 - mgy, yhi = sy1 + mgy;
     // vertex_window: lo.x >= (sx - 0.5) / s, hi.x <= sx / s; lo.y >= (H - 1 - sy) / s, hi.y <= (H - 0.5 - sy) / s
     const float sf = (float)s;
-    const int X0 = max(0, (int)floorf((xlo - 1.0f) / sf)), X1 = min(a.ws - 1, (int)floorf(xhi / sf));
-    const int Y0 = max(0, (int)floorf((Hf - 1.0f - yhi) / sf)), Y1 = min(a.hs - 1, (int)floorf((Hf - ylo) / sf));
+    const int X0u = (int)floorf((xlo - 1.0f) / sf), X1u = (int)floorf(xhi / sf);
+    const int Y0u = (int)floorf((Hf - 1.0f - yhi) / sf), Y1u = (int)floorf((Hf - ylo) / sf);
+    const int X0 = max(0, X0u), X1 = min(a.ws - 1, X1u), Y0 = max(0, Y0u), Y1 = min(a.hs - 1, Y1u);
     // Every vertex's computed z is at least the corners' minimum less the rounding of two dot products
     // (<= 6 eps Bz); the margin 1e-5 Bz covers that.  |x|, |y| after the projection are below Pbx, Pby.
     // (The fragment test of a fastdiv pose relies on these bounds too: pcore_fdiv.h, frag_barycentrics.)
     const bool fastdiv = lzmin - 1.0e-5f * Bz >= 1.0f && Bz < 0x1p40f && Pbx < 0x1p40f && Pby < 0x1p40f;
     // interior: the box [xlo, xhi] x [ylo, yhi] holds every vertex's computed screen coordinates (it is what the window
-    // above is made from) and lies inside the image; NaN bounds fail
-    const bool interior = fastdiv && xlo >= 0.0f && xhi <= Wf - 1.0f && ylo >= 0.0f && yhi <= Hf - 1.0f;
+    // above is made from) and lies inside the image; NaN bounds fail.  And none of the four clamps of the window to the
+    // sampled image binds, so the window is the box's own and holds every triangle's window unclipped (raster_phase,
+    // WHOLE).  With ws = W / s and hs = ceil(H / s) the first clamp binds where xlo < 1 and the last where s divides H and
+    // H - ylo rounds to H; with any other ws, hs more would: such a pose is fastdiv only.  (With those ws, hs the two
+    // clamps never cut a triangle's window -- A0 >= 0 and B1 <= (H - 1) / s = hs - 1 whatever the box -- so the test
+    // buys a proof that does not lean on how the host derives ws and hs, not correctness.)
+    const bool unclamped = X0u >= 0 && X1u <= a.ws - 1 && Y0u >= 0 && Y1u <= a.hs - 1;
+    const bool interior = fastdiv && unclamped && xlo >= 0.0f && xhi <= Wf - 1.0f && ylo >= 0.0f && yhi <= Hf - 1.0f;
     return SampleWin{X0, Y0, max(0, X1 - X0 + 1), max(0, Y1 - Y0 + 1), fastdiv ? 1 : 0, sparse, interior ? 1 : 0};
 }
 
@@ -696,10 +752,11 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
     int wave_bad = 0, wave_pts = 0;
     int32_t* cid = nullptr;
     if constexpr (COLOUR) cid = a.cid + (size_t)pose * nsamp;
-    auto chunk = [&](const SampleWin& sw) __attribute__((always_inline)) {
+    // `whole`: std::true_type where sw is the pose's window itself (raster_phase, WHOLE)
+    auto chunk = [&](const SampleWin& sw, auto whole) __attribute__((always_inline)) {
         const int tn = sw.nx * sw.ny;  // samples of the chunk (tile)
         for (int i = tid; i < tn; i += kThreads) sm.zbuf[i] = INT_MAX;
-        if (sw.interior) raster_phase<STRIDE, false, 2>(a, sm, pose, sw, nullptr, fp);
+        if (sw.interior) raster_phase<STRIDE, false, 2, decltype(whole)::value>(a, sm, pose, sw, nullptr, fp);
         else if (sw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, sw, nullptr, fp);
         else raster_phase<STRIDE, false, 0>(a, sm, pose, sw, nullptr, fp);
         fp.mark(2);
@@ -862,14 +919,14 @@ __device__ __forceinline__ void fused_pose(const FusedArgs& a, const FusedSmem& 
         wave_bad += __builtin_amdgcn_readfirstlane(my_bad);
     };
     if (pw.nx * pw.ny <= cap) {
-        chunk(pw);  // the window fits the tile (the common case: its own copy of the code, no loop state)
+        chunk(pw, std::true_type{});  // the window fits the tile (the common case: its own copy of the code, no loop state)
     } else {
         const int cw = min(pw.nx, cap), ch = max(1, cap / max(cw, 1));  // chunk columns / rows
         for (int r0 = 0; r0 < pw.ny; r0 += ch)
             for (int c0 = 0; c0 < pw.nx; c0 += cw) {
                 if (r0 > 0 || c0 > 0) __syncthreads();  // the previous chunk's points are processed
                 chunk(SampleWin{pw.x0 + c0, pw.y0 + r0, min(cw, pw.nx - c0), min(ch, pw.ny - r0), pw.fastdiv,
-                                pw.sparse, pw.interior});
+                                pw.sparse, pw.interior}, std::false_type{});
             }
     }
     // per-wave totals
@@ -1060,10 +1117,10 @@ render_cloud_kernel(FusedArgs a) {
     // one chunk of the window (fused_pose's chunking): raster into the tile, then the chunk's valid samples appended
     // in row-major order -- row bands of whole window rows (column blocks when a row exceeds the tile) keep the
     // reference's row-major compaction order (no valid sample lies outside the window)
-    auto chunk = [&](const SampleWin& cw) __attribute__((always_inline)) {
+    auto chunk = [&](const SampleWin& cw, auto whole) __attribute__((always_inline)) {
         const int tn = cw.nx * cw.ny;
         for (int i = tid; i < tn; i += kThreads) sm.zbuf[i] = INT_MAX;
-        if (cw.interior) raster_phase<STRIDE, false, 2>(a, sm, pose, cw, nullptr, fp);
+        if (cw.interior) raster_phase<STRIDE, false, 2, decltype(whole)::value>(a, sm, pose, cw, nullptr, fp);
         else if (cw.fastdiv) raster_phase<STRIDE, false, 1>(a, sm, pose, cw, nullptr, fp);
         else raster_phase<STRIDE, false, 0>(a, sm, pose, cw, nullptr, fp);
         __syncthreads();
@@ -1104,13 +1161,13 @@ render_cloud_kernel(FusedArgs a) {
         }
     };
     if (sw.nx * sw.ny <= cap) {
-        chunk(sw);
+        chunk(sw, std::true_type{});
     } else {
         const int cw = min(sw.nx, cap), ch = max(1, cap / max(cw, 1));
         for (int r0 = 0; r0 < sw.ny; r0 += ch)
             for (int c0 = 0; c0 < sw.nx; c0 += cw)
                 chunk(SampleWin{sw.x0 + c0, sw.y0 + r0, min(cw, sw.nx - c0), min(ch, sw.ny - r0), sw.fastdiv,
-                                sw.sparse, sw.interior});
+                                sw.sparse, sw.interior}, std::false_type{});
     }
     if (tid == 0) a.cloud_count[pose] = carry_s < a.cloud_cap ? carry_s : a.cloud_cap;
 }
